@@ -2,7 +2,12 @@
 """Benchmark of the geometric-distillation student step (BASELINE.json metric: image-pairs/s at 518^2,
 ViT-B/14 + LoRA) on N MI355X GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, loss, config);
+everything else it can measure or check (the objects listed under "Extra objects" below) runs with --full only.  --dump-outputs DIR writes
+what the last timed step computed (loss, per-pair loss terms, pre-clip gradient norm, the flat gradient and the updated flat parameters) as
+DIR/<name>.npy; the weights and batches come from fixed seeds, so two runs with the same arguments see the same inputs.
 
 N > 1 without WORLD_SIZE in the environment: this process only LAUNCHES `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` as a child (before any GPU call) and exits with its code — one rank per GPU over RCCL; under torchrun
@@ -17,7 +22,7 @@ The headline engine is `tf32h`: fp32 tensors, every matrix product (GEMMs, atten
 accumulation — i.e. the precision class the reference's benched MASt3R path computes in (torch.backends.cuda.matmul.allow_tf32, dust3r/croco/models/
 croco.py:12; gfx950 has no TF32 MFMA).  The bf16 engine (16-bit storage, faster, narrower than the reference) is reported beside it as config.bf16_run.
 
-Extra objects on the line:
+Extra objects on the line (--full):
   roofline              the dominant kernel (persistent gemm_nt, MFMA-bound) from HIP events around every launch in the timed region
   roofline_cost_volume  the HBM-bound fused cost-volume KL, timed on its own after the run (also as roofline.cost_volume_kl_fwd);
                         frac = bytes that must move / time / peak, for the benched row masks and for every row kept (`unmasked`)
@@ -32,6 +37,7 @@ Extra objects on the line:
   other_configs         short runs of BASELINE configs 3 / 5-like and of the reference's own token geometry
   comm                  N > 1: all-reduce time of the two gradient chunks and the exposed fraction of the step
   cpu_baseline          the CPU oracle on a bounded sample of the same workload, rank 0 / N=1 only
+  fp16_range            tf32h: scaled fp16 gradient operands clamped / below fp16's normal range over the warm-up + timed steps
 """
 import argparse
 import json
@@ -71,7 +77,7 @@ def parse():
     ap.add_argument("--geometry", default="shared", choices=["shared", "reference"],
                     help="shared: one 37x37-token forward per image feeds all extractors (BASELINE headline); reference: the "
                          "reference's geometry (80x80-token forwards for the keypoint features + the teacher-grid forward)")
-    ap.add_argument("--gemm-shapes", action="store_true", help="per-shape gemm_nt breakdown on stderr")
+    ap.add_argument("--gemm-shapes", action="store_true", help="per-shape gemm_nt breakdown on stderr (with --full)")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--steps-only", action="store_true", help="profiling aid: the timed steps and nothing else (no cost-volume roofline leg, "
                     "no CPU legs, no companion runs): a kernel trace of this run holds the step's kernels only")
@@ -82,7 +88,14 @@ def parse():
                          "one gd_flat_allreduce (C ABI, RCCL reduce-scatter + all-gather) after the backward")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL); 'gloo' lets two "
                     "ranks share one GPU for a functional check of the N>1 path")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: the GEMM roofline from HIP events "
+                    "around every launch of the timed steps, fp16_range, the cost-volume roofline leg, parity + cpu_baseline, the companion engine "
+                    "runs and other_configs, and (N > 1) the comm A/B runs; the --no-* / --steps-only switches narrow it down as before")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss, loss "
+                    "terms, gradient norm, flat gradient, updated flat parameters) as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full:          # a plain run: the timed steps and the headline line, nothing else
+        args.steps_only = True
     if args.steps_only:
         args.no_cpu_baseline = args.no_extras = args.no_kernel_events = True
     return args
@@ -168,7 +181,14 @@ class Job:
                                                            teacher_patch=tp)) for i in range(2)]
 
     def step(self, i):
-        return self.eng.fit_step(self.batches[i % len(self.batches)], self.reducer)[0]
+        self.last = self.eng.fit_step(self.batches[i % len(self.batches)], self.reducer)      # (loss, terms, pre-clip gradient norm)
+        return self.last[0]
+
+    def step_outputs(self):
+        """What the last step handed its caller — loss, per-pair loss terms, pre-clip gradient norm — and what it left in the flat buffers: the
+        exchanged gradient and the parameters after clip + AdamW."""
+        loss, terms, gnorm = self.last
+        return {"loss": loss, **terms, "grad_norm": gnorm, "flat_grad": self.flat["g"], "flat_params": self.flat["p"]}
 
     def timed(self, steps, warmup, dev, prof=None):
         """-> (seconds for `steps` steps = max over ranks, last loss); barrier + synchronize on both sides."""
@@ -185,6 +205,27 @@ class Job:
         dt = time.perf_counter() - t0
         ops.set_gemm_profiler(None)
         return dp.max_over_ranks(dt, dev), loss
+
+
+def dump_outputs(outdir, arrays, budget=60 * 10 ** 6):
+    """arrays: name -> tensor, written as outdir/<name>.npy in float32 (float64 stays float64), `budget` bytes in all: smaller arrays first, each
+    allowed an equal share of what is left; one larger than its share is replaced by a fixed, seeded sample of its flattened elements (the same
+    indices on every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    left = budget
+    for i, name in enumerate(sorted(host, key=lambda n: host[n].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def gemm_roofline(prof, dtype, dt, steps):
@@ -253,21 +294,25 @@ def main():
 
     if world > 1 and args.reserve_cus:
         dp.reserve_cus_for_collectives(args.reserve_cus)
+    torch.manual_seed(0)       # the engine's initial weights (the batches carry their own seeds): the same inputs on every run
     job = Job(backbone, variant, args.dtype, args.geometry, P, img, N, dev, rank, world, weights=weights, exchange=args.exchange)
     eng, hw = job.eng, job.hw
     prof = None if args.no_kernel_events else ops.GemmProfiler()
-    if args.dtype == "tf32h":
+    range_check = args.full and args.dtype == "tf32h"
+    if range_check:
         job.eng.range_report()                       # reset: the report below covers the warm-up + timed steps of this run
     dt, loss = job.timed(args.steps, args.warmup, dev, prof)
     pairs_per_s = P * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job.step_outputs())
     # tf32h: how many scaled fp16 gradient operands saturated / fell below fp16's normal range over these steps (device counters, ONE host read here)
     fp16_range = dict(job.eng.range_report(), steps=args.steps + args.warmup,
                       what="scaled fp16 gradient operands of the tf32h engine: elements clamped at +-65504 / elements below 2^-14 after the block's "
                            "power-of-two scale (DESIGN.md 4, range contract).  Counted: the cast kernels, the LayerNorm backward's fp16 copy, and the two "
                            "dX products per block that leave their GEMM as saturating fp16 (counted where the LayerNorm backward reads them); NOT counted: "
-                           "the attention output gradient and the GELU-gated gradient, fp16 C stores consumed by MFMA kernels only") if args.dtype == "tf32h" else None
+                           "the attention output gradient and the GELU-gated gradient, fp16 C stores consumed by MFMA kernels only") if range_check else None
 
-    comm = comm_report(job, args, dev, dt) if world > 1 else None
+    comm = comm_report(job, args, dev, dt) if world > 1 and args.full else None
 
     out = None
     if rank == 0:
