@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("GD_HIP_LIB") or os.path.join(_HERE, "lib", "libgd_hip
 _lib = None
 
 F32, BF16, F16 = 0, 1, 3
+MATCH_COLS = 1       # gd_match_argmax flags: also the column argmax (include/gd_hip.h GD_MATCH_COLS)
 
 c_int, c_long, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -140,6 +141,11 @@ SIGNATURES = {
     "gd_nms_keypoints": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_void_p]),
     "gd_nn_argmax": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gd_match_argmax_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gd_match_argmax": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gd_transfer_argmax_workspace_bytes": (c_size_t, [c_int]),
+    "gd_transfer_argmax": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gd_point_cloud_to_depth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_post_process_depth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gd_post_process_depth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float,

@@ -1307,3 +1307,94 @@ def cast(x, dtype, scale=1.0):
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
     check(lib().gd_cast(ptr(x), ptr(out), x.numel(), float(scale), dtype_code(x), dtype_code(out), stream()), "gd_cast")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- correspondence evaluation
+class MatchResult(tuple):
+    """(row_idx, col_idx, mutual, row_score, col_score) of `match_argmax`; fields that were not asked for are None."""
+    __slots__ = ()
+    _fields = ("row_idx", "col_idx", "mutual", "row_score", "col_score")
+
+    def __new__(cls, *vals):
+        return tuple.__new__(cls, vals)
+
+    row_idx = property(lambda s: s[0])
+    col_idx = property(lambda s: s[1])
+    mutual = property(lambda s: s[2])
+    row_score = property(lambda s: s[3])
+    col_score = property(lambda s: s[4])
+
+
+_MATCH_TARGET = 32768.0      # fp16 operands: max |x| * s in (2^14, 2^15] — half of fp16's range is left as headroom, nothing can saturate
+
+
+def _f16_operand(x):
+    """f32 [rows, D] -> (fp16 copy under a power-of-two scale, device scalar 1/s).  A non-finite element is an error, not a NaN scale."""
+    sc = amax_scale(x, _MATCH_TARGET)
+    _req(bool(torch.isfinite(sc[0]).item()), "match_argmax: the operand holds a non-finite element")
+    out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    check(lib().gd_cast_f16_ex(ptr(x), ptr(out), x.shape[0], x.shape[1], x.stride(0), 1.0, ptr(sc[0:1]), None, stream()), "gd_cast_f16_ex")
+    return out, sc[1:2]
+
+
+def match_argmax(a, b, *, both=True, precision="f16", want_scores=False, want_mutual=False):
+    """Nearest neighbours by dot product in both directions from one pass (gd_match_argmax): a [M, D], b [N, D] (D a multiple of 8) ->
+    MatchResult(row_idx [M] int64 = argmax_j a_i . b_j, col_idx [N] int64 = argmax_i a_i . b_j (both=True), mutual [M] bool =
+    (col_idx[row_idx] == arange(M)) (want_mutual), row_score / col_score fp32 (want_scores)).  Ties pick the smallest index, as
+    torch.argmax does.  precision "f32": exact fp32 products of fp32 inputs; "f16": fp32 inputs rounded to fp16 under a power-of-two
+    per-tensor scale (the reference's TF32 class; argmax is scale-invariant) or fp16 inputs as they are; "bf16": bf16 inputs."""
+    _req(precision in ("f32", "f16", "bf16"), f"match_argmax: precision must be 'f32', 'f16' or 'bf16', not {precision!r}")
+    _req(a.dim() == 2 and b.dim() == 2, "match_argmax: a and b must be 2-D [rows, D]")
+    _req(a.shape[1] == b.shape[1], f"match_argmax: descriptor widths differ ({a.shape[1]} vs {b.shape[1]})")
+    (M, D), N = a.shape, b.shape[0]
+    _req(M > 0 and N > 0 and D > 0 and D % 8 == 0, f"match_argmax: need non-empty inputs and D a multiple of 8 (M={M} N={N} D={D})")
+    _req(not want_mutual or both, "match_argmax: the mutual mask needs both directions")
+    _req(a.is_cuda and b.is_cuda, "match_argmax: a and b must be CUDA tensors")
+    inv_a = inv_b = None
+    if precision == "f32":
+        _req(a.dtype == torch.float32 and b.dtype == torch.float32, "match_argmax: precision 'f32' takes fp32 inputs")
+        a, b = a.contiguous(), b.contiguous()
+    elif precision == "bf16":
+        _req(a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16, "match_argmax: precision 'bf16' takes bf16 inputs")
+        a, b = a.contiguous(), b.contiguous()
+    else:
+        _req(a.dtype in (torch.float32, torch.float16) and b.dtype in (torch.float32, torch.float16), "match_argmax: precision 'f16' takes fp32 or fp16 inputs")
+        if a.dtype == torch.float32:
+            a, inv_a = _f16_operand(a.contiguous())
+        if b.dtype == torch.float32:
+            b, inv_b = _f16_operand(b.contiguous())
+        a, b = a.contiguous(), b.contiguous()
+    dev = a.device
+    flags = _lib.MATCH_COLS if both else 0
+    ws = torch.empty(lib().gd_match_argmax_workspace_bytes(M, N, flags), dtype=torch.uint8, device=dev)
+    row = torch.empty(M, dtype=torch.int64, device=dev)
+    col = torch.empty(N, dtype=torch.int64, device=dev) if both else None
+    mut = torch.empty(M, dtype=torch.bool, device=dev) if want_mutual else None
+    rs = torch.empty(M, dtype=torch.float32, device=dev) if want_scores else None
+    cs = torch.empty(N, dtype=torch.float32, device=dev) if want_scores and both else None
+    check(lib().gd_match_argmax(ptr(a), ptr(b), M, N, D, dtype_code(a), flags, ptr(inv_a), ptr(inv_b), ptr(row), ptr(rs), ptr(col), ptr(cs),
+                                ptr(mut), ptr(ws), stream()), "gd_match_argmax")
+    return MatchResult(row, col, mut, rs, cs)
+
+
+def transfer_argmax(S, img_hw, patch, stride, *, want_score=False):
+    """Semantic-transfer argmax over the upsampled, edge-padded score field (gd_transfer_argmax): S [K, gh, gw] fp32 (or [K, gh, pitch]
+    with only the first gw = 1 + (img_w - patch) // stride columns used) -> xy [K, 2] int64 (x, y) of the raster-first maximum of
+    pad(interpolate(S, (ds_h, ds_w), bilinear, align_corners=True)), ds = ((img - patch) // stride) * stride + 1, edge pads patch // 2
+    top / left; (xy, score [K]) with want_score."""
+    img_h, img_w = (int(v) for v in img_hw)
+    _req(S.dtype == torch.float32 and S.dim() == 3, "transfer_argmax: S must be a 3-D fp32 tensor [K, gh, gw]")
+    _req(patch > 0 and stride > 0 and img_h >= patch and img_w >= patch, f"transfer_argmax: bad geometry image {img_h}x{img_w} patch {patch} stride {stride}")
+    K, gh, pitch = S.shape
+    gw = 1 + (img_w - patch) // stride
+    _req(gh == 1 + (img_h - patch) // stride and pitch >= gw,
+         f"transfer_argmax: score grid {gh}x{pitch} does not match image {img_h}x{img_w} at patch {patch}, stride {stride} "
+         f"(expected {1 + (img_h - patch) // stride}x{gw})")
+    _req(S.is_cuda, "transfer_argmax: S must be a CUDA tensor")
+    S = S.contiguous()
+    xy = torch.empty(K, 2, dtype=torch.int64, device=S.device)
+    sc = torch.empty(K, dtype=torch.float32, device=S.device) if want_score else None
+    ws = torch.empty(lib().gd_transfer_argmax_workspace_bytes(K), dtype=torch.uint8, device=S.device)
+    check(lib().gd_transfer_argmax(ptr(S), K, gh, gw, pitch, img_h, img_w, int(patch), int(stride), ptr(xy), ptr(sc), ptr(ws), stream()),
+          "gd_transfer_argmax")
+    return (xy, sc) if want_score else xy

@@ -423,6 +423,30 @@ int gd_nn_argmax(const float* queries, const float* database, const unsigned cha
 int gd_point_cloud_to_depth(const float* points, const float* K, float* depth, float* cnt_ws, int P, int Np, int w,
                             int h, void* stream);
 
+/* Correspondence evaluation (src/evaluate_timm.py EvaluationCallback, :591-730).
+ * gd_match_argmax: the OnePose++ matching block (src/evaluate_timm.py:166-179: two chunked `d @ templates.T` + argmax, one per
+ *   direction) as ONE MFMA pass over S = A . B^T with the argmax fused into the epilogue: S never reaches memory.  A [M,D], B [N,D]
+ *   row-major (D contiguous, D a multiple of 8, 16-byte aligned), dtype GD_F32 (exact fp32 products), GD_F16 (the tf32h precision
+ *   class; operands may carry per-tensor positive scales, see inv_scale_*) or GD_BF16.  row_idx [M] int64 = argmax_j S[i][j];
+ *   with flags & GD_MATCH_COLS also col_idx [N] int64 = argmax_i S[i][j] and (nullable) mutual [M] bytes = (col_idx[row_idx[i]] == i).
+ *   Ties pick the smallest index (torch.argmax's first occurrence); the result does not depend on scheduling.  row_score / col_score
+ *   (nullable, fp32) = the maximum times *inv_scale_a * *inv_scale_b (device scalars, nullable = 1).  workspace: caller-owned,
+ *   gd_match_argmax_workspace_bytes(M, N, flags) bytes.
+ * gd_transfer_argmax: the semantic-transfer argmax (src/evaluate_timm.py:531-547) without the upsampled feature map: bilinear
+ *   upsampling and edge padding are linear, so q . up(T) = up(q . T).  S [K, gh, pitch] fp32 (columns x < gw used) is the K x grid
+ *   score map; the field is S upsampled (bilinear, align_corners=True) to ds = ((img - patch) // stride) * stride + 1 per axis, then
+ *   edge-padded by patch // 2 on the top / left and img - ds - patch // 2 on the bottom / right; every pixel is evaluated.  xy [K,2]
+ *   int64 = (x, y) of the raster-first maximum; score [K] (nullable) its value.  The grid must be 1 + (img - patch) // stride per axis.
+ *   workspace: gd_transfer_argmax_workspace_bytes(K) bytes. */
+#define GD_MATCH_COLS 1
+size_t gd_match_argmax_workspace_bytes(int M, int N, int flags);
+int gd_match_argmax(const void* A, const void* B, int M, int N, int D, int dtype, int flags, const float* inv_scale_a,
+                    const float* inv_scale_b, long long* row_idx, float* row_score, long long* col_idx, float* col_score,
+                    unsigned char* mutual, void* workspace, void* stream);
+size_t gd_transfer_argmax_workspace_bytes(int K);
+int gd_transfer_argmax(const float* S, int K, int gh, int gw, int pitch, int img_h, int img_w, int patch, int stride,
+                       long long* xy, float* score, void* workspace, void* stream);
+
 /* post_process_depth (utils/functions.py:262-345) on P rasterised depth maps [P,H,W]: max-pool closing, two hole-filling
  * passes, median (kernel_size in {3, 5}), bilateral, guided filter (guidance = the bilateral map, input = the median map, as the
  * call site passes them), 3-sigma outlier replacement, joint bilateral.  The four kornia filters are restated from kornia's
