@@ -104,6 +104,13 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_f32<0x140, 0xF>(v);   // row_mirror
     return v;
 }
+__device__ __forceinline__ float row16_max(float v) {
+    v = fmaxf(v, dpp_f32<0xB1, 0xF>(v));
+    v = fmaxf(v, dpp_f32<0x4E, 0xF>(v));
+    v = fmaxf(v, dpp_f32<0x141, 0xF>(v));
+    v = fmaxf(v, dpp_f32<0x140, 0xF>(v));
+    return v;
+}
 // sum over the 64 lanes, result uniform (via lane 63)
 __device__ __forceinline__ float wave_sum(float v) {
     v = row16_sum(v);
@@ -115,6 +122,18 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The MFMA LoRA rank update on fp16 operands (gemm_nt, lora_rt == 8): LoRA B starts at zero and moves by ~lr = 1e-5 per step, which rounded to fp16
+// as it is sits among the subnormals (spacing 2^-24: 3e-3 relative at 1e-5, 3e-2 at 1e-6).  B goes in times 2^s and the rank update's accumulator
+// contribution is taken times 2^-s: both exact.  s brings the largest |B| of a wave's columns into [2^13, 2^14) (fp16's normals reach 2^-14, so B values
+// down to 2^-27 of the largest keep 11 bits); 0 for an all-zero B; clamped to [-16, 40] so that an accumulator scaled by 2^s stays finite.
+// (With KPL = 8 fp16 values per fragment, only lane group g = 0 — lanes 0..15 — holds live k rows of the update: the largest |B| is a row16_max
+// read from lane 0.)
+__device__ __forceinline__ int f16_lora_shift(float bmax) {
+    if (!(bmax > 0.f)) return 0;
+    const int e = __builtin_amdgcn_frexp_expf(bmax);      // bmax = f 2^e, f in [0.5, 1)
+    return min(max(14 - e, -16), 40);
 }
 
 // exact-erf GELU and its derivative (torch.nn.GELU default, approximate='none')

@@ -191,13 +191,30 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_nt_kernel(GemmNtParams p)
         const float* lB = lT + BM * 8;
         const float ia = 1.0f / (p.alpha_dev ? p.alpha * *p.alpha_dev : p.alpha);
         const bool live = KPL * g < 8;
+        // fp16 operands: B goes in times 2^bsh (f16_lora_shift, gd_common.h) and the accumulators are taken to that scale and back around the
+        // update (powers of two: exact)
+        constexpr bool F16B = std::is_same<T, f16>::value;
+        int bsh = 0;
+        if constexpr (F16B) {
+            float bm = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int k = 0; k < KPL; ++k) bm = fmaxf(bm, live ? fabsf(lB[((KPL * g + k) & 7) * BN + wn * 64 + j * 16 + fr]) : 0.f);
+            bsh = f16_lora_shift(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, row16_max(bm)), 0)));
+            const float up = __builtin_amdgcn_ldexpf(1.0f, bsh);
+#pragma unroll
+            for (int i = 0; i < WMT; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] *= up;
+        }
         Frag bf[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int k = 0; k < KPL; ++k) {
                 const float x = lB[((KPL * g + k) & 7) * BN + wn * 64 + j * 16 + fr];
-                bf[j][k] = (T)(live ? x : 0.f);
+                bf[j][k] = (T)(live ? (F16B ? __builtin_amdgcn_ldexpf(x, bsh) : x) : 0.f);
             }
 #pragma unroll
         for (int i = 0; i < WMT; ++i) {
@@ -207,6 +224,13 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_nt_kernel(GemmNtParams p)
             for (int k = 0; k < KPL; ++k) af[k] = (T)(live ? ia * tr[k] : 0.f);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = Mma<T>::mma(af, bf[j], acc[i][j]);
+        }
+        if constexpr (F16B) {
+            const float down = __builtin_amdgcn_ldexpf(1.0f, -bsh);
+#pragma unroll
+            for (int i = 0; i < WMT; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] *= down;
         }
     }
 

@@ -181,17 +181,27 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmNtParams p) {
             const unsigned baddr = lds_off(smem + LORA_OFF + BM * 32) + 4 * (((KPL * g) & 7) * BN + wn * 64 + 4 * fr);
             const unsigned taddr = lds_off(smem + LORA_OFF) + 4 * ((wm * WMT * 16 + fr) * 8 + ((KPL * g) & 7));
             Frag bf[4];
+            constexpr bool F16B = std::is_same<T, f16>::value;      // fp16 operands: B times 2^bsh (f16_lora_shift, gd_common.h)
+            int bsh = 0;
             {
                 f32x4 q0, q1, q2, q3, q4 = {0.f, 0.f, 0.f, 0.f}, q5 = q4, q6 = q4, q7 = q4;
                 GD_DSR128(q0, baddr, 0); GD_DSR128(q1, baddr, 1024); GD_DSR128(q2, baddr, 2048); GD_DSR128(q3, baddr, 3072);
                 if (KPL == 8) { GD_DSR128(q4, baddr, 4096); GD_DSR128(q5, baddr, 5120); GD_DSR128(q6, baddr, 6144); GD_DSR128(q7, baddr, 7168); }
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5), "+v"(q6), "+v"(q7));
                 const f32x4 qs[8] = {q0, q1, q2, q3, q4, q5, q6, q7};
+                if constexpr (F16B) {      // (acc is still zero: only the rank update carries the scale, undone below)
+                    float bm = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int k = 0; k < KPL; ++k) bm = fmaxf(bm, live ? fabsf(qs[k][j]) : 0.f);
+                    bsh = f16_lora_shift(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, row16_max(bm)), 0)));
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int k = 0; k < KPL; ++k) {
-                        const float x = live ? qs[k][j] : 0.f;
+                        const float x = live ? (F16B ? __builtin_amdgcn_ldexpf(qs[k][j], bsh) : qs[k][j]) : 0.f;
                         bf[j][k] = (L3 && g == 2) ? (T)(x - (float)(T)x) : (T)x;
                     }
             }
@@ -211,6 +221,13 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmNtParams p) {
             }
             GD_LT(0, 0) GD_LT(1, 512) GD_LT(2, 1024) GD_LT(3, 1536) GD_LT(4, 2048) GD_LT(5, 2560) GD_LT(6, 3072) GD_LT(7, 3584)
 #undef GD_LT
+            if constexpr (F16B) {
+                const float rs = __builtin_amdgcn_ldexpf(1.0f, -bsh);
+#pragma unroll
+                for (int i = 0; i < WMT; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] *= rs;
+            }
         }
         const int co0 = ((g ^ sa) * 16), co1 = (((4 + g) ^ sa) * 16);
         FragHead P, Q;

@@ -43,6 +43,16 @@ def _opw(w, fmt):
     return ops.split3(w, "w") if fmt == "x3" else ops.cast16(w)
 
 
+LORA_B_SHIFT = 12
+
+
+def _opw_lora_b(b):
+    """LoRA B (f32 [2r, *]) as the fp16 right operand of the tf32h backward's dt product -> (operand, the host alpha that undoes its scale).
+    B starts at zero and moves by ~lr per step: cast as it is, it would sit among fp16's subnormals (3e-3 relative at 1e-5).  Times 2^12 it keeps
+    11 bits from 2^-26 up to |B| = 16 (past that it saturates); the product takes alpha = 2^-12 (both powers of two: exact)."""
+    return ops.cast16(b, scale=2.0 ** LORA_B_SHIFT), 2.0 ** -LORA_B_SHIFT
+
+
 def _mm(x, plan, key, xs=None, sc=None, **kw):
     """x . W^T with the plan's frozen weight `key`: one GEMM in the f32 / bf16 engines; in the tf32x / tf32h engines the weight was put into
     the operand format once (plan['x3'] = "x3" | "h") and the activation goes in on the way (xs: its formatted copy, when the caller already
@@ -399,10 +409,11 @@ class _BlockFn(torch.autograd.Function):
                     dqkv_s = dqkv if fmt == "h" else _opa(dqkv, fmt, sc)           # (tf32h: already fp16, already times s)
                     btz = torch.zeros(bt_qv.shape[0], 3 * D, dtype=torch.float32, device=dqkv.device)
                     btz[:, :2 * D] = bt_qv
-                    dt = ops.gemm_nt(dqkv_s, _opw(btz, fmt), out_dtype=torch.float32, alpha_dev=ad)      # [M, 2r]
+                    bw, ba = _opw_lora_b(btz) if fmt == "h" else (_opw(btz, fmt), 1.0)
+                    dt = ops.gemm_nt(dqkv_s, bw, out_dtype=torch.float32, alpha=ba, alpha_dev=ad)      # [M, 2r]
                 else:      # first trainable block: the dk third of dqkv was never written — split the (dq, dv) view only
-                    dt = ops.gemm_nt(dqv if fmt == "h" else _opa(dqv, fmt, sc), _opw(bt_qv.contiguous(), fmt), out_dtype=torch.float32,
-                                     alpha_dev=ad)
+                    bw, ba = _opw_lora_b(bt_qv.float().contiguous()) if fmt == "h" else (_opw(bt_qv.contiguous(), fmt), 1.0)
+                    dt = ops.gemm_nt(dqv if fmt == "h" else _opa(dqv, fmt, sc), bw, out_dtype=torch.float32, alpha=ba, alpha_dev=ad)
                 if fmt == "h":       # dqv carries the block's scale s: contract into a scratch and add it unscaled
                     gs = ops.gemm_tn(t, dqv)
                     z_bt.add_(gs * sc[1])
