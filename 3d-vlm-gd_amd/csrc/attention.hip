@@ -15,388 +15,9 @@
 // Replaces F.scaled_dot_product_attention inside timm's Attention (restated from
 // vggt/layers/attention.py:51-71): softmax((q*scale) k^T) v with scale = head_dim^-0.5.
 // qkv is the packed [B, N, 3, H, 64] output of the QKV GEMM; o is [B, N, H*64]; lse is [B, H, N] (natural log).
-#include "gd_common.h"
-#include <type_traits>
-#include <stdlib.h>
-
-#define HD 64
-
-// ---- split-precision path (dtype code GD_F32X3): fp32 tensors in memory, every MFMA operand as a (hi, lo) pair of bf16 fragments,
-// hi = bf16(x), lo = bf16(x - hi), and every product as the three bf16 MFMAs  lo_a hi_b + hi_a lo_b + hi_a hi_b  (all of a . b except
-// lo_a lo_b: ~4e-6 relative, TF32 ~3e-4) — 3 x 16 MFMA cycles per 32-wide chunk against 8 x 32 for the exact-f32 MFMA.  The same
-// kernels, instantiated on the tag type `x3` (a 4-byte element: pointer arithmetic is fp32's); only the traits below differ.
-struct x3 { float v; };
-struct X3Frag { bf16x8 hi, lo; };
-template <typename T> struct IsX3 { static constexpr bool v = false; };
-template <> struct IsX3<x3> { static constexpr bool v = true; };
-template <> struct Mma<x3> {
-    static constexpr int KC = 32;
-    typedef X3Frag Frag;
-    static __device__ __forceinline__ f32x4 mma(const Frag& a, const Frag& b, f32x4 c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, c, 0, 0, 0);      // small terms first
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ X3Frag x3_split(const float (&x)[8]) {
-    X3Frag f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        f.hi[k] = (bf16)x[k];
-        f.lo[k] = (bf16)(x[k] - (float)f.hi[k]);
-    }
-    return f;
-}
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // bare v_exp_f32
-// max over the 4 lanes {l, l^16, l^32, l^48} with the gfx950 row-swap instructions (VALU; a ds_bpermute pair costs two
-// dependent LDS round trips in the middle of the softmax)
-// (The two results of a swap are taken out as SCALARS before they are reinterpreted: __builtin_bit_cast applied to an ext-vector element
-// expression a[1] reads element 0 on ROCm 7.2's clang — rounds 1-3 shipped `fmaxf(bit_cast(a[0]), bit_cast(a[1]))`, which compiled to a[0] alone:
-// every lane got lane group 0's maximum instead of the query's.  A uniform but arbitrary reference point still gives the right o and lse — which
-// is why every bf16 / f32 test passed — but it does not bound p by 2^ATT_THR, and fp16 p overflowed to inf on peaked rows: found by round 4's
-// adversarial fp16 cases, tests/test_gpu_attention.py::test_attention_reference_point_moves[float16].)
-__device__ __forceinline__ float quad_rows_max(float v) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned a0 = a[0], a1 = a[1];
-    v = fmaxf(__builtin_bit_cast(float, a0), __builtin_bit_cast(float, a1));
-    const unsigned w = __builtin_bit_cast(unsigned, v);
-    const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-    const unsigned b0 = b[0], b1 = b[1];
-    return fmaxf(__builtin_bit_cast(float, b0), __builtin_bit_cast(float, b1));
-}
-
-// ---- softmax with a LAGGED reference point (forward) ---------------------------------------------------------------
-// The score accumulators are started from -m (the MFMA's C operand: a persistent register quartet per query tile, no
-// instruction), with q pre-multiplied by scale*log2(e), so a finished accumulator is already  s*c2 - m  and p is ONE
-// v_exp per score — the online softmax's subtract / scale FMA is gone, and so is its running row sum: the row sums come
-// out of the PV product as one more MFMA per k-chunk against an all-ones A fragment (they are then the sums of exactly
-// the bf16-rounded p that multiply V).  m is a reference point, not the exact running maximum: the first tile sets it to
-// the tile's row maximum, later tiles only RAISE it, and only when a score exceeds it by more than ATT_THR (p <= 2^THR
-// otherwise): a wave-uniform branch that is almost never taken after the first tiles.  Any reference point gives the same
-// o = sum p v / sum p and lse = m + log2 sum p; the first-tile rule keeps sum p >= 1, so nothing can underflow to 0 / 0.
-#ifndef ATT_THR
-#define ATT_THR 8.0f
-#endif
-// the two 16-bit element types share every layout: bf16 (bf16 engine) and fp16 (tf32h engine: TF32's significand; conversions saturate)
-template <typename T> struct V16;
-template <> struct V16<bf16> { typedef bf16x8 T8; typedef bf16x4 T4; };
-template <> struct V16<f16> { typedef f16x8 T8; typedef f16x4 T4; };
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag frag_scale(typename Mma<T>::Frag f, float a);
-template <typename T> __device__ __forceinline__ typename V16<T>::T8 frag_scale16(typename V16<T>::T8 f, float a) {
-    typename V16<T>::T8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = from_f32<T>((float)f[k] * a);
-    return o;
-}
-template <> __device__ __forceinline__ bf16x8 frag_scale<bf16>(bf16x8 f, float a) { return frag_scale16<bf16>(f, a); }
-template <> __device__ __forceinline__ f16x8 frag_scale<f16>(f16x8 f, float a) { return frag_scale16<f16>(f, a); }
-template <> __device__ __forceinline__ f32x4 frag_scale<float>(f32x4 f, float a) { return f * a; }
-template <> __device__ __forceinline__ X3Frag frag_scale<x3>(X3Frag f, float a) {      // scale the fp32 value, split again
-    float x[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = ((float)f.hi[k] + (float)f.lo[k]) * a;
-    return x3_split(x);
-}
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag frag_ones();
-template <> __device__ __forceinline__ bf16x8 frag_ones<bf16>() {
-    const bf16 o = (bf16)1.0f;
-    return bf16x8{o, o, o, o, o, o, o, o};
-}
-template <> __device__ __forceinline__ f16x8 frag_ones<f16>() {
-    const f16 o = (f16)1.0f;
-    return f16x8{o, o, o, o, o, o, o, o};
-}
-template <> __device__ __forceinline__ f32x4 frag_ones<float>() { return f32x4{1.f, 1.f, 1.f, 1.f}; }
-template <> __device__ __forceinline__ X3Frag frag_ones<x3>() {
-    X3Frag f = {};
-    f.hi = frag_ones<bf16>();
-    return f;
-}
-
-// s[qt][kt] hold s*c2 - m of a 64-key tile (TAIL: keys >= N get -1e30).  Updates m / negm (and rescales o, l) when the
-// tile's maximum moved the reference point, then turns the scores into p in place.
-template <bool TAIL>
-__device__ __forceinline__ void softmax_lagged(f32x4 (&s)[2][4], float (&m)[2], f32x4 (&negm)[2], f32x4 (&oacc)[4][2],
-                                               f32x4 (&lacc)[2], bool first, int k0, int g, int N) {
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        float tmax = -1e30f;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (TAIL && k0 + kt * 16 + g * 4 + r >= N) s[qt][kt][r] = -1e30f;
-                tmax = fmaxf(tmax, s[qt][kt][r]);
-            }
-        // the cross-lane maximum is only needed when SOME lane of the wave sees a score above the threshold (if no lane's own 16 scores exceed
-        // it, no query's 64 do): the steady state pays one compare and a wave-uniform branch, not the two lane exchanges
-        if (first || __any(tmax > ATT_THR)) {
-            tmax = quad_rows_max(tmax);
-            const bool need = first || tmax > ATT_THR;
-            const float d = need ? tmax : 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s[qt][kt][r] -= d;
-            m[qt] += d;
-            negm[qt] = f32x4{-m[qt], -m[qt], -m[qt], -m[qt]};
-            if (!first) {                                  // (first tile: o and l are still zero, and d may be negative)
-                const float alpha = fast_exp2(-d);
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) oacc[dt][qt] *= alpha;
-                lacc[qt] *= alpha;
-            }
-        }
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[qt][kt][r] = fast_exp2(s[qt][kt][r]);
-    }
-}
-
-template <typename T> struct AT;
-// LDS tiles of 64 rows.  bf16: rows are 128 bytes UNPADDED and the 16-byte chunk index is XOR-ed with
-// sw(row) = ((row >> 1) & 3) << 1.  One image serves both read patterns conflict-free (PMC before: 33-43 % of the LDS cycles
-// of these kernels were bank-conflict cycles with padded 144-byte rows / the GEMM's (row >> 1) & 7 swizzle):
-//   * ds_read_b128 fragment reads (rows 16 k + c, chunk 4 u + g): the hardware serves lanes {0-3, 12-15, 20-27} together —
-//     rows c in {0..3, 12..15} at chunk q and rows {4..11} at chunk q ^ 1; rows of equal parity share a 128-byte bank
-//     half and get the XOR values {0, 2, 4, 6} resp. {4, 6, 0, 2}: eight distinct chunks per half;
-//   * ds_read_b64_tr_b16 transpose reads (32 lanes = 8 consecutive rows x the chunk PAIR {2 dt, 2 dt + 1}): the four rows of
-//     equal parity need four different pairs — XOR by an even number that differs between them, which an odd XOR ((row >> 1) & 7
-//     has them) does not give.
-struct AT16 {
-    static constexpr int NF = 2;        // fragments per 64-wide contraction
-    static constexpr int ROWB = 128;    // LDS row: 64 el * 2 B
-    static constexpr int CPR = 8;       // 16-byte chunks per 64-element row
-    static constexpr int EPC = 8;       // elements per chunk
-    static __device__ __forceinline__ int sw(int row) { return ((row >> 1) & 3) << 1; }
-};
-template <> struct AT<bf16> : AT16 {};
-template <> struct AT<f16> : AT16 {};
-template <> struct AT<float> {
-    static constexpr int NF = 4;
-    static constexpr int ROWB = 272;    // 64 el * 4 B + 16 pad, linear
-    static constexpr int CPR = 16;
-    static constexpr int EPC = 4;
-    static __device__ __forceinline__ int sw(int) { return 0; }
-};
-
-// x3: an LDS row is 256 bytes = 16 positions of 16 bytes: plane pl (0 hi, 1 lo), chunk q (8 bf16 each) sits at position
-// (8 pl + q) ^ (row & 15) — the sixteen rows 16 k + c that a ds_read_b128 lane group reads at one logical chunk land on sixteen
-// different positions; row and row + 16 share the swizzle (the transpose reads rely on it).
-template <> struct AT<x3> {
-    static constexpr int NF = 2;        // (hi, lo) fragment pairs per 64-wide contraction
-    static constexpr int ROWB = 256;
-    static constexpr int CPR = 16;      // 16-byte chunks per 64-float GLOBAL row
-    static constexpr int EPC = 4;
-    static __device__ __forceinline__ int sw(int row) { return row & 15; }
-};
-
-// four C-layout tiles that span 64 contraction indices (index = 16*tile + 4*g + r) -> B fragment u
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag acc_to_bfrag(const f32x4 (&t)[4], int u);
-template <> __device__ __forceinline__ bf16x8 acc_to_bfrag<bf16>(const f32x4 (&t)[4], int u) {
-    const f32x4 a = t[2 * u], b = t[2 * u + 1];
-    return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-template <> __device__ __forceinline__ f16x8 acc_to_bfrag<f16>(const f32x4 (&t)[4], int u) {
-    const f32x4 a = t[2 * u], b = t[2 * u + 1];
-    // plain conversions (v_cvt_pk_f16_f32; a saturating clamp per element made these issue-port-bound kernels 13-26 % slower): p <= 2^ATT_THR
-    // in the forward, p <= 1 and |dS| <= |dP - delta| in the backward, where dP is a 64-term dot product of the SCALED dout (|dout| s <= 8,
-    // vit.py) with v — five orders of magnitude below 65504 for any realistic v
-    return f16x8{(f16)a[0], (f16)a[1], (f16)a[2], (f16)a[3], (f16)b[0], (f16)b[1], (f16)b[2], (f16)b[3]};
-}
-template <> __device__ __forceinline__ f32x4 acc_to_bfrag<float>(const f32x4 (&t)[4], int u) { return t[u]; }
-template <> __device__ __forceinline__ X3Frag acc_to_bfrag<x3>(const f32x4 (&t)[4], int u) {
-    const f32x4 a = t[2 * u], b = t[2 * u + 1];
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return x3_split(x);
-}
-
-// matching A fragment from a transposed LDS tile row (64 contraction indices contiguous)
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag load_tfrag(const char* row, int u, int g);
-template <> __device__ __forceinline__ bf16x8 load_tfrag<bf16>(const char* row, int u, int g) {
-    const bf16x4 a = *(const bf16x4*)(row + (32 * u + 4 * g) * 2);
-    const bf16x4 b = *(const bf16x4*)(row + (32 * u + 16 + 4 * g) * 2);
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-template <> __device__ __forceinline__ f16x8 load_tfrag<f16>(const char* row, int u, int g) {
-    const f16x4 a = *(const f16x4*)(row + (32 * u + 4 * g) * 2);
-    const f16x4 b = *(const f16x4*)(row + (32 * u + 16 + 4 * g) * 2);
-    return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-template <> __device__ __forceinline__ f32x4 load_tfrag<float>(const char* row, int u, int g) {
-    return *(const f32x4*)(row + (16 * u + 4 * g) * 4);
-}
-
-// natural fragment u (16 bytes) of a [row][64] LDS tile row / global row
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag load_nfrag(const char* row, int u, int g) {
-    return *(const typename Mma<T>::Frag*)(row + u * 64 + g * 16);
-}
-
-// natural fragment u of row `row` of an LDS tile (chunk 4 u + g, swizzled)
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag lds_nfrag(const char* tile, int row, int u, int g) {
-    return *(const typename Mma<T>::Frag*)(tile + row * AT<T>::ROWB + (((u * 4 + g) ^ AT<T>::sw(row)) * 16));
-}
-
-template <> __device__ __forceinline__ X3Frag load_nfrag<x3>(const char* row, int u, int g) {      // GLOBAL fp32 row: floats 32 u + 8 g .. + 7
-    const f32x4 a = *(const f32x4*)(row + (32 * u + 8 * g) * 4), b = *(const f32x4*)(row + (32 * u + 8 * g + 4) * 4);
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return x3_split(x);
-}
-template <> __device__ __forceinline__ X3Frag lds_nfrag<x3>(const char* tile, int row, int u, int g) {
-    const char* r = tile + row * AT<x3>::ROWB;
-    X3Frag f;
-    f.hi = *(const bf16x8*)(r + (((u * 4 + g) ^ AT<x3>::sw(row)) * 16));
-    f.lo = *(const bf16x8*)(r + (((8 + u * 4 + g) ^ AT<x3>::sw(row)) * 16));
-    return f;
-}
-
-// Tile staging, split T14-style: `tile_load` issues the global loads of a 64 x 64-element tile into registers
-// (rows >= nvalid read as zero) and `tile_store` writes them to LDS later — as a natural tile sN[row][64]
-// and/or a transposed tile sT[col][row] — so the next tile's HBM/L2 latency hides under the current tile's MFMAs.
-template <typename T, int NT = 256> struct TileRegs { uint4 v[AT<T>::CPR * 64 / NT]; };
-
-template <typename T, int NT = 256>
-__device__ __forceinline__ void tile_load(TileRegs<T, NT>& r, const char* gbase, long ld_b, int row0, int nvalid) {
-    constexpr int CPR = AT<T>::CPR, NCH = CPR * 64 / NT;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int ch = threadIdx.x + NT * i, rr = ch / CPR, cc = ch % CPR;
-        r.v[i] = (row0 + rr < nvalid) ? *(const uint4*)(gbase + (long)(row0 + rr) * ld_b + cc * 16) : make_uint4(0, 0, 0, 0);
-    }
-}
-// The same through a buffer resource (backward kernels): rows >= nvalid lie past the resource's last record and read as zero
-// in hardware — no per-chunk compare / exec mask / zero-fill and no 64-bit address arithmetic in the tile loop (that was 28 of the
-// dQ loop's 76 non-transcendental VALU instructions); the per-thread byte offsets are loop-invariant, the tile adds row0 * ld.
-template <typename T, int NT = 256> struct TileSrc {
-    __amdgpu_buffer_rsrc_t rs;
-    int off[AT<T>::CPR * 64 / NT];
-    int ld;
-};
-template <typename T, int NT = 256>
-__device__ __forceinline__ void tile_src_init(TileSrc<T, NT>& src, const char* gbase, long ld_b, int nvalid) {
-    constexpr int CPR = AT<T>::CPR, NCH = CPR * 64 / NT;
-    src.rs = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, (short)0, (int)((long)(nvalid - 1) * ld_b + 64 * (long)sizeof(T)), 0x00020000);
-    src.ld = (int)ld_b;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int ch = threadIdx.x + NT * i, rr = ch / CPR, cc = ch % CPR;
-        src.off[i] = rr * (int)ld_b + cc * 16;
-    }
-}
-template <typename T, int NT = 256>
-__device__ __forceinline__ void tile_load(TileRegs<T, NT>& r, const TileSrc<T, NT>& src, int row0) {
-    constexpr int NCH = AT<T>::CPR * 64 / NT;
-    const int base = row0 * src.ld;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-        r.v[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(src.rs, src.off[i] + base, 0, 0));
-}
-template <typename T, bool NAT, bool TRN, int NT = 256>
-__device__ __forceinline__ void tile_store(const TileRegs<T, NT>& r, char* sN, char* sT) {
-    constexpr int CPR = AT<T>::CPR, EPC = AT<T>::EPC, ROWB = AT<T>::ROWB, NCH = CPR * 64 / NT;
-    if constexpr (std::is_same<T, x3>::value) {      // four floats -> four hi + four lo bf16 (8 bytes each): half `cc & 1` of bf16 chunk `cc >> 1`
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int ch = threadIdx.x + NT * i, rr = ch / CPR, cc = ch % CPR;
-            const f32x4 x = __builtin_bit_cast(f32x4, r.v[i]);
-            bf16x4 hi, lo;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { hi[k] = (bf16)x[k]; lo[k] = (bf16)(x[k] - (float)hi[k]); }
-            char* row = sN + rr * ROWB + 8 * (cc & 1);
-            *(bf16x4*)(row + (((cc >> 1) ^ AT<x3>::sw(rr)) * 16)) = hi;
-            *(bf16x4*)(row + (((8 + (cc >> 1)) ^ AT<x3>::sw(rr)) * 16)) = lo;
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int ch = threadIdx.x + NT * i, rr = ch / CPR, cc = ch % CPR;
-        if (NAT) *(uint4*)(sN + rr * ROWB + ((cc ^ AT<T>::sw(rr)) * 16)) = r.v[i];
-        if (TRN) {
-            const T* e = (const T*)&r.v[i];
-#pragma unroll
-            for (int k = 0; k < EPC; ++k) *(T*)(sT + (cc * EPC + k) * ROWB + rr * (int)sizeof(T)) = e[k];
-        }
-    }
-}
-
-// The "transposed operand" A[row = column c of the tile][k-slot = tile row]:
-//   bf16: read straight from the NATURAL tile with ds_read_b64_tr_b16 (hardware 4x16 transpose per 16-lane group:
-//         lane 4q+p supplies the address of block row q, columns 4p..4p+3; lane i receives column i of the 4 rows)
-//   f32 : 16-byte read from an explicitly transposed LDS tile.
-template <typename T> struct TOp;
-template <typename T> struct TOp16 {
-    static constexpr bool kNeedT = false;
-    static __device__ __forceinline__ typename V16<T>::T8 load(const char* sN, const char*, int dt, int u, int g, int lane) {
-        typedef __attribute__((ext_vector_type(4))) short s16x4;
-        const int i = lane & 15, q = i >> 2, p = i & 3;
-        const int row = 32 * u + 4 * g + q;                         // (row + 16 has the same swizzle)
-        const char* a0 = sN + row * AT<bf16>::ROWB + (((2 * dt + (p >> 1)) ^ AT<bf16>::sw(row)) * 16) + 8 * (p & 1);
-        const char* a1 = a0 + 16 * AT<bf16>::ROWB;
-        const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-        const s16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 z = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-        return __builtin_bit_cast(typename V16<T>::T8, z);
-    }
-};
-template <> struct TOp<bf16> : TOp16<bf16> {};
-template <> struct TOp<f16> : TOp16<f16> {};
-template <> struct TOp<x3> {      // both planes straight from the natural tile, as bf16
-    static constexpr bool kNeedT = false;
-    static __device__ __forceinline__ bf16x8 plane(const char* sN, int pl, int dt, int u, int g, int lane) {
-        typedef __attribute__((ext_vector_type(4))) short s16x4;
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const int i = lane & 15, q = i >> 2, p = i & 3;
-        const int row = 32 * u + 4 * g + q;                         // (row + 16 has the same swizzle)
-        const char* a0 = sN + row * AT<x3>::ROWB + (((8 * pl + 2 * dt + (p >> 1)) ^ AT<x3>::sw(row)) * 16) + 8 * (p & 1);
-        const char* a1 = a0 + 16 * AT<x3>::ROWB;
-        const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-        const s16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-        const s16x8 z = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-        return __builtin_bit_cast(bf16x8, z);
-    }
-    static __device__ __forceinline__ X3Frag load(const char* sN, const char*, int dt, int u, int g, int lane) {
-        X3Frag f;
-        f.hi = plane(sN, 0, dt, u, g, lane);
-        f.lo = plane(sN, 1, dt, u, g, lane);
-        return f;
-    }
-};
-template <> struct TOp<float> {
-    static constexpr bool kNeedT = true;
-    static __device__ __forceinline__ f32x4 load(const char*, const char* sT, int dt, int u, int g, int lane) {
-        return load_tfrag<float>(sT + (dt * 16 + (lane & 15)) * AT<float>::ROWB, u, g);
-    }
-};
-#define TSZ(T) (TOp<T>::kNeedT ? 64 * AT<T>::ROWB : 16)
-
-template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
-template <> __device__ __forceinline__ void store4<x3>(x3* p, f32x4 v) { *(f32x4*)p = v; }
-template <> __device__ __forceinline__ void store4<bf16>(bf16* p, f32x4 v) {
-    *(bf16x4*)p = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-template <> __device__ __forceinline__ void store4<f16>(f16* p, f32x4 v) {
-    *(f16x4*)p = f16_sat4(v[0], v[1], v[2], v[3]);
-}
+#include "attn_common.h"
 
 // ------------------------------------------------------------------------------------------ forward
-// (x-block, head, image) of this workgroup.  The x-blocks of one (image, head) all sweep the same K / V (or Q / dO) rows;
-// in plain launch order they are dealt round-robin over the eight XCDs, so every XCD's L2 pulls every (image, head)'s
-// operands over the fabric (PMC: 2.2-2.5 GB per launch against 0.4-0.5 GB of operands).  The linear launch index is
-// re-mapped so that each XCD gets a contiguous run of (image, head) groups, x-block fastest.
-__device__ __forceinline__ void attn_block_coords(int& xb, int& h, int& b) {
-    const int nx = gridDim.x, ny = gridDim.y;
-    const int lin = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const int r = xcd_remap(lin, nx * ny * gridDim.z);
-    xb = r % nx;
-    h = (r / nx) % ny;
-    b = r / (nx * ny);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const T* qkv, T* o, float* lse, int N, int H, float scale) {
     constexpr int NF = AT<T>::NF, ROWB = AT<T>::ROWB;
@@ -506,12 +127,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const T* qkv, T* o, fl
 // V transpose reads (ds_read_b64_tr_b16) stay conflict-free.  All LDS reads are inline asm (a ds_read the compiler can see
 // gets an `s_waitcnt vmcnt` to the most recent LDS-DMA in front of it); one counted vmcnt wait + one barrier per tile.
 // Key rows past N are clamped to row N-1: their scores are masked in the (compile-time) tail tile, so p = 0 for them.
-#define ADS_R128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define ADS_TR64(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-// ... with the offset as a compile-time expression (the steady-state loop below: slot * tile size + row-group offset, one address register per lane)
-#define ADS_R128I(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
-#define ADS_TR64I(dst, addr, imm) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
-typedef __attribute__((ext_vector_type(2))) unsigned a_u32x2;
 // Round 6: the tiles whose two-ahead prefetch is a full tile run in groups of THREE with the ring slot as a compile-time constant — every LDS read is
 // base register + immediate (no per-tile address arithmetic on the vector ALU) and the slot / wait-kind / full-tile / rotation tests leave the loop:
 // ~30 scalar instructions per tile instead of ~60 (the round-5 loop executed 1.40 scalar per MFMA, profiles/r05_pmc_attention_stall.json; the non-MFMA
@@ -696,10 +311,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const T* qkv, T* o
             if (!live) return;
             const unsigned ak0 = lds0 + ka0, ak1 = lds0 + ka1;
             f32x4 kr[4][2];
-            ADS_R128I(kr[0][0], ak0, S * TILE + 0);    ADS_R128I(kr[0][1], ak1, S * TILE + 0);
-            ADS_R128I(kr[1][0], ak0, S * TILE + 2048); ADS_R128I(kr[1][1], ak1, S * TILE + 2048);
-            ADS_R128I(kr[2][0], ak0, S * TILE + 4096); ADS_R128I(kr[2][1], ak1, S * TILE + 4096);
-            ADS_R128I(kr[3][0], ak0, S * TILE + 6144); ADS_R128I(kr[3][1], ak1, S * TILE + 6144);
+            ADS_R128(kr[0][0], ak0, S * TILE + 0);    ADS_R128(kr[0][1], ak1, S * TILE + 0);
+            ADS_R128(kr[1][0], ak0, S * TILE + 2048); ADS_R128(kr[1][1], ak1, S * TILE + 2048);
+            ADS_R128(kr[2][0], ak0, S * TILE + 4096); ADS_R128(kr[2][1], ak1, S * TILE + 4096);
+            ADS_R128(kr[3][0], ak0, S * TILE + 6144); ADS_R128(kr[3][1], ak1, S * TILE + 6144);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kr[0][0]), "+v"(kr[0][1]), "+v"(kr[1][0]), "+v"(kr[1][1]), "+v"(kr[2][0]), "+v"(kr[2][1]),
                          "+v"(kr[3][0]), "+v"(kr[3][1]));
             f32x4 s[2][4];
@@ -714,8 +329,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const T* qkv, T* o
                 }
             a_u32x2 vr[4][2][2];   // [dt][u][row half]
 #define ADS_VI(dt)                                                                                                                   \
-            ADS_TR64I(vr[dt][0][0], lds0 + va[dt], (3 + S) * TILE + 0);    ADS_TR64I(vr[dt][0][1], lds0 + va[dt], (3 + S) * TILE + 2048);       \
-            ADS_TR64I(vr[dt][1][0], lds0 + va[dt], (3 + S) * TILE + 4096); ADS_TR64I(vr[dt][1][1], lds0 + va[dt], (3 + S) * TILE + 6144);
+            ADS_TR64(vr[dt][0][0], lds0 + va[dt], (3 + S) * TILE + 0);    ADS_TR64(vr[dt][0][1], lds0 + va[dt], (3 + S) * TILE + 2048);       \
+            ADS_TR64(vr[dt][1][0], lds0 + va[dt], (3 + S) * TILE + 4096); ADS_TR64(vr[dt][1][1], lds0 + va[dt], (3 + S) * TILE + 6144);
             ADS_VI(0) ADS_VI(1) ADS_VI(2) ADS_VI(3)
 #undef ADS_VI
             softmax_lagged<false>(s, m, negm, oacc, lacc, first, 0, g, N);
@@ -763,27 +378,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const T* qkv, T* o
         for (int dt = 0; dt < 4; ++dt) store4<T>(orow + dt * 16 + g * 4, oacc[dt][qt] * inv);
         if (g == 0) lse[((long)b * H + h) * N + q] = (m[qt] + log2f(lsum)) * 0.6931471805599453f;
     }
-}
-
-// dot of two operand fragments (the 16 bytes a lane holds of a row), fp32
-__device__ __forceinline__ float frag_dot(bf16x8 a, bf16x8 b) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s = fmaf((float)a[k], (float)b[k], s);
-    return s;
-}
-__device__ __forceinline__ float frag_dot(f16x8 a, f16x8 b) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s = fmaf((float)a[k], (float)b[k], s);
-    return s;
-}
-__device__ __forceinline__ float frag_dot(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-__device__ __forceinline__ float frag_dot(const X3Frag& a, const X3Frag& b) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s = fmaf((float)a.hi[k] + (float)a.lo[k], (float)b.hi[k] + (float)b.lo[k], s);
-    return s;
 }
 
 // ------------------------------------------------------------------------------------------ backward: dQ
@@ -933,8 +527,6 @@ __global__ __launch_bounds__(256, IsX3<T>::v ? 1 : 2) void attn_bwd_dq_kernel(co
 // attn_bwd_dq_kernel with the K / V tiles on the forward's three-slot LDS-DMA ring (two tiles ahead, one counted vmcnt wait + one barrier per tile, no
 // staging registers) and every LDS read inline asm, pipelined by hand under the MFMAs — the dK/dV kernel's recipe (attn_bwd_dkv_dma_kernel, below).
 // Key rows past N are clamped to row N - 1 in the partial last tile (the register-staged kernel stages zeros): their dS is set to zero there, as before.
-#define ADS_R128V(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-#define ADS_TR64V(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
 template <typename T>      // bf16 | f16
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const T* qkv, const T* o, const T* dout, const float* lse, float* delta, T* dqkv, int N, int H,
                                                                  float scale) {
@@ -1053,7 +645,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const T* qkv, c
         a_u32x2 tr_[2][2];
         f32x4 ds[2][2];      // [query tile][key tile & 1]
         Frag df[2];
-#define DQ_RK(kt, S) ADS_R128V(rk0[S], ka0, kt * 2048); ADS_R128V(rk1[S], ka1, kt * 2048); ADS_R128V(rv0[S], va0, kt * 2048); ADS_R128V(rv1[S], va1, kt * 2048);
+#define DQ_RK(kt, S) ADS_R128(rk0[S], ka0, kt * 2048); ADS_R128(rk1[S], ka1, kt * 2048); ADS_R128(rv0[S], va0, kt * 2048); ADS_R128(rv1[S], va1, kt * 2048);
 #define DQ_WAIT_K(n, S) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(rk0[S]), "+v"(rk1[S]), "+v"(rv0[S]), "+v"(rv1[S]) : "i"(n));
 #define DQ_CK(kt, S)                                                                                                                    \
         _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                                                              \
@@ -1069,7 +661,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const T* qkv, c
         }
 #define DQ_FRAGS()                                                                                                                      \
         _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) { const f32x4 t4[4] = {ds[qt][0], ds[qt][1], ds[qt][0], ds[qt][1]}; df[qt] = acc_to_bfrag<T>(t4, 0); }
-#define DQ_RT(u, dt, S) ADS_TR64V(tr_[S][0], kbase + ta[dt], u * 4096); ADS_TR64V(tr_[S][1], kbase + ta[dt], u * 4096 + 2048);
+#define DQ_RT(u, dt, S) ADS_TR64(tr_[S][0], kbase + ta[dt], u * 4096); ADS_TR64(tr_[S][1], kbase + ta[dt], u * 4096 + 2048);
 #define DQ_WAIT_T(n, S) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(tr_[S][0]), "+v"(tr_[S][1]) : "i"(n));
 #define DQ_MQ(dt, S)                                                                                                                    \
         {                                                                                                                               \
@@ -1388,8 +980,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const T* qkv, 
         Frag pf[2], sf[2];
         constexpr int NRA = DK ? 6 : 3, NRT = DK ? 4 : 2;            // LDS reads per RA / RT
 #define DKV_RA(qt, S)                                                                                                                   \
-        ADS_R128V(aq0[S], qa0, qt * 2048); ADS_R128V(aq1[S], qa1, qt * 2048); ADS_R128V(anl[S], cb, qt * 64);                           \
-        if (DK) { ADS_R128V(ad0[S], da0, qt * 2048); ADS_R128V(ad1[S], da1, qt * 2048); ADS_R128V(and_[S], cb, 256 + qt * 64); }
+        ADS_R128(aq0[S], qa0, qt * 2048); ADS_R128(aq1[S], qa1, qt * 2048); ADS_R128(anl[S], cb, qt * 64);                           \
+        if (DK) { ADS_R128(ad0[S], da0, qt * 2048); ADS_R128(ad1[S], da1, qt * 2048); ADS_R128(and_[S], cb, 256 + qt * 64); }
 #define DKV_WAIT_A(n, S)                                                                                                                \
         if (DK) asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(aq0[S]), "+v"(aq1[S]), "+v"(ad0[S]), "+v"(ad1[S]), "+v"(anl[S]), "+v"(and_[S]) : "i"(n)); \
         else asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(aq0[S]), "+v"(aq1[S]), "+v"(anl[S]) : "i"(n));
@@ -1420,8 +1012,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const T* qkv, 
             if (DK) { const f32x4 d4[4] = {dsv[kt][0], dsv[kt][1], dsv[kt][0], dsv[kt][1]}; sf[kt] = acc_to_bfrag<T>(d4, 0); }          \
         }
 #define DKV_RT(u, dt, S)                                                                                                                \
-        ADS_TR64V(tdr[S][0], dtb + ta[dt], u * 4096); ADS_TR64V(tdr[S][1], dtb + ta[dt], u * 4096 + 2048);                              \
-        if (DK) { ADS_TR64V(tqr[S][0], qtb + ta[dt], u * 4096); ADS_TR64V(tqr[S][1], qtb + ta[dt], u * 4096 + 2048); }
+        ADS_TR64(tdr[S][0], dtb + ta[dt], u * 4096); ADS_TR64(tdr[S][1], dtb + ta[dt], u * 4096 + 2048);                              \
+        if (DK) { ADS_TR64(tqr[S][0], qtb + ta[dt], u * 4096); ADS_TR64(tqr[S][1], qtb + ta[dt], u * 4096 + 2048); }
 #define DKV_WAIT_T(n, S)                                                                                                                \
         if (DK) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(tdr[S][0]), "+v"(tdr[S][1]), "+v"(tqr[S][0]), "+v"(tqr[S][1]) : "i"(n));    \
         else asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(tdr[S][0]), "+v"(tdr[S][1]) : "i"(n));
@@ -1483,190 +1075,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const T* qkv, 
     }
 }
 
-// ------------------------------------------------------------------------------------------ teacher cross-view maps
-// VGGT teacher -> distillation target.  The reference's global blocks return, per head, the two
-// cross-view softmax maps  softmax(q[prefix:N/2] k[N/2+prefix:]^T * scale / temperature)  and the mirrored one
-// (vggt/layers/attention.py:51-85), i.e. [2B, H, n, n] fp32 per block (480 MB per pair at n = 1369, H = 16), which are then
-// averaged over heads (src/finetune_timm_vggt.py:390-392) and over the selected blocks (vggt/models/aggregator.py:273).
-// Here only the averaged [2B, n, n] map ever exists: pass 1 = flash-style row statistics per (direction, head, query)
-// (log2 domain), pass 2 = one block per (128 queries x 64 keys) output tile loops over the heads, recomputes the
-// S^T tile on the MFMA and accumulates exp2(s - lse) in registers; `weight` (= 1 / (H * blocks)) and `accumulate`
-// fold the layer mean into the same buffer.  q, k: [B, H, N, 64] (after q/k-norm and RoPE).
-template <typename T>
-__global__ __launch_bounds__(256, 2) void cva_stats_kernel(const T* q, const T* k, float* lse2, int B, int H, int N, int prefix,
-                                                           float c2) {
-    constexpr int NF = AT<T>::NF, ROWB = AT<T>::ROWB;
-    typedef typename Mma<T>::Frag Frag;
-    __shared__ __attribute__((aligned(16))) char sK[64 * ROWB];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
-    const int n = N / 2 - prefix, dir = blockIdx.z / B, b = blockIdx.z % B, h = blockIdx.y;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const long ld_b = (long)HD * sizeof(T);
-    const char* qb = (const char*)q + (((long)b * H + h) * N + (dir ? N / 2 + prefix : prefix)) * ld_b;
-    const char* kb = (const char*)k + (((long)b * H + h) * N + (dir ? prefix : N / 2 + prefix)) * ld_b;
-    Frag qf[2][NF];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const int qi = q0 + qt * 16 + c;
-#pragma unroll
-        for (int u = 0; u < NF; ++u) {
-            Frag z = {};
-            qf[qt][u] = qi < n ? load_nfrag<T>(qb + (long)qi * ld_b, u, g) : z;
-        }
-    }
-    float m[2] = {-1e30f, -1e30f}, l[2] = {0.f, 0.f};
-    TileRegs<T> rk;
-    tile_load<T>(rk, kb, ld_b, 0, n);
-    for (int k0 = 0; k0 < n; k0 += 64) {
-        __syncthreads();
-        tile_store<T, true, false>(rk, sK, nullptr);
-        __syncthreads();
-        if (k0 + 64 < n) tile_load<T>(rk, kb, ld_b, k0 + 64, n);
-        f32x4 s[2][4];
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            Frag kf[NF];
-#pragma unroll
-            for (int u = 0; u < NF; ++u) kf[u] = lds_nfrag<T>(sK, kt * 16 + c, u, g);
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) {
-                f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int u = 0; u < NF; ++u) a = Mma<T>::mma(kf[u], qf[qt][u], a);
-                s[qt][kt] = a;
-            }
-        }
-        const bool tail = k0 + 64 > n;
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            float tmax = -1e30f;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (tail && k0 + kt * 16 + g * 4 + r >= n) s[qt][kt][r] = -1e30f;
-                    tmax = fmaxf(tmax, s[qt][kt][r]);
-                }
-            tmax = quad_rows_max(tmax);
-            const float mn = fmaxf(m[qt], tmax * c2);
-            float ps = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ps += fast_exp2(fmaf(s[qt][kt][r], c2, -mn));
-            l[qt] = l[qt] * fast_exp2(m[qt] - mn) + ps;
-            m[qt] = mn;
-        }
-    }
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const int qi = q0 + qt * 16 + c;
-        l[qt] += __shfl_xor(l[qt], 16, 64);
-        l[qt] += __shfl_xor(l[qt], 32, 64);
-        if (qi < n && g == 0) lse2[(((long)dir * B + b) * H + h) * n + qi] = m[qt] + log2f(l[qt]);
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void cva_emit_kernel(const T* q, const T* k, const float* lse2, float* out, int B, int H, int N,
-                                                          int prefix, float c2, float weight, int accumulate) {
-    constexpr int NF = AT<T>::NF, ROWB = AT<T>::ROWB;
-    typedef typename Mma<T>::Frag Frag;
-    __shared__ __attribute__((aligned(16))) char sK[64 * ROWB];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
-    const int n = N / 2 - prefix, dir = blockIdx.z / B, b = blockIdx.z % B;
-    const int q0 = blockIdx.x * 128 + wave * 32, k0 = blockIdx.y * 64;
-    const long ld_b = (long)HD * sizeof(T);
-    const long head_b = (long)N * ld_b;
-    const char* qb = (const char*)q + (((long)b * H) * N + (dir ? N / 2 + prefix : prefix)) * ld_b;
-    const char* kb = (const char*)k + (((long)b * H) * N + (dir ? prefix : N / 2 + prefix)) * ld_b;
-    const float* lb = lse2 + (((long)dir * B + b) * H) * n;
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) acc[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    TileRegs<T> rk;
-    tile_load<T>(rk, kb, ld_b, k0, n);
-    for (int h = 0; h < H; ++h) {
-        __syncthreads();
-        tile_store<T, true, false>(rk, sK, nullptr);
-        __syncthreads();
-        if (h + 1 < H) tile_load<T>(rk, kb + (long)(h + 1) * head_b, ld_b, k0, n);
-        Frag qf[2][NF];
-        float ls[2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            const int qi = q0 + qt * 16 + c;
-            ls[qt] = qi < n ? lb[(long)h * n + qi] : 0.f;
-#pragma unroll
-            for (int u = 0; u < NF; ++u) {
-                Frag z = {};
-                qf[qt][u] = qi < n ? load_nfrag<T>(qb + (long)h * head_b + (long)qi * ld_b, u, g) : z;
-            }
-        }
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            Frag kf[NF];
-#pragma unroll
-            for (int u = 0; u < NF; ++u) kf[u] = lds_nfrag<T>(sK, kt * 16 + c, u, g);
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) {
-                f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int u = 0; u < NF; ++u) a = Mma<T>::mma(kf[u], qf[qt][u], a);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[qt][kt][r] += fast_exp2(fmaf(a[r], c2, -ls[qt]));
-            }
-        }
-    }
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const int qi = q0 + qt * 16 + c;
-        if (qi >= n) continue;
-        float* orow = out + (((long)dir * B + b) * n + qi) * n;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kj = k0 + kt * 16 + g * 4 + r;
-                if (kj < n) orow[kj] = weight * acc[qt][kt][r] + (accumulate ? orow[kj] : 0.f);
-            }
-    }
-}
-
-extern "C" size_t gd_cross_view_attn_workspace_bytes(int B, int H, int N, int prefix) {
-    const int n = N / 2 - prefix;
-    return n > 0 ? (size_t)2 * B * H * n * sizeof(float) : 0;
-}
-
-extern "C" int gd_cross_view_attn(const void* q, const void* k, float* out, int B, int H, int N, int prefix, int head_dim,
-                                  float scale, float temperature, float weight, int accumulate, int dtype, void* workspace,
-                                  void* stream) {
-    GD_REQUIRE(B > 0 && H > 0 && N > 0 && N % 2 == 0 && prefix >= 0 && N / 2 - prefix > 0,
-               "gd_cross_view_attn: bad shape B=%d H=%d N=%d prefix=%d", B, H, N, prefix);
-    GD_REQUIRE(head_dim == HD, "gd_cross_view_attn: head_dim must be 64 (got %d)", head_dim);
-    GD_REQUIRE(dtype == GD_F32 || dtype == GD_BF16, "gd_cross_view_attn: bad dtype %d", dtype);
-    GD_REQUIRE(temperature > 0.f, "gd_cross_view_attn: temperature must be positive");
-    GD_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && workspace != nullptr,
-               "gd_cross_view_attn: q, k must be 16-byte aligned, workspace non-null");
-    const int n = N / 2 - prefix;
-    const float c2 = scale / temperature * 1.4426950408889634f;
-    float* lse2 = (float*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 g1(gd_cdiv(n, 128), H, 2 * B), g2(gd_cdiv(n, 128), gd_cdiv(n, 64), 2 * B);
-    if (dtype == GD_BF16) {
-        hipLaunchKernelGGL(cva_stats_kernel<bf16>, g1, dim3(256), 0, s, (const bf16*)q, (const bf16*)k, lse2, B, H, N, prefix, c2);
-        hipLaunchKernelGGL(cva_emit_kernel<bf16>, g2, dim3(256), 0, s, (const bf16*)q, (const bf16*)k, lse2, out, B, H, N, prefix, c2, weight, accumulate);
-    } else {
-        hipLaunchKernelGGL(cva_stats_kernel<float>, g1, dim3(256), 0, s, (const float*)q, (const float*)k, lse2, B, H, N, prefix, c2);
-        hipLaunchKernelGGL(cva_emit_kernel<float>, g2, dim3(256), 0, s, (const float*)q, (const float*)k, lse2, out, B, H, N, prefix, c2, weight, accumulate);
-    }
-    GD_LAUNCH_OK();
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------ C ABI
+template <typename T> constexpr bool kIs16 = std::is_same<T, bf16>::value || std::is_same<T, f16>::value;
+
+// the element type of a dtype code, handed to `f` as a null pointer of that type (GD_F16 = the tf32h engine: fp16 q / k / v / p with TF32's significand on
+// the bf16 kernels' layouts; in the backward dout arrives times a power of two, the caller's gd_amax_scale, and dqkv leaves with it)
+template <typename F> static void attn_with_type(int dtype, F f) {
+    if (dtype == GD_BF16) f((bf16*)nullptr);
+    else if (dtype == GD_F16) f((f16*)nullptr);
+    else if (dtype == GD_F32X3) f((x3*)nullptr);
+    else f((float*)nullptr);
+}
+
+template <typename T>
+static void attn_fwd_launch(const void* qkv, void* o, float* lse, int B, int N, int H, float scale, hipStream_t s) {
+    const dim3 grid(gd_cdiv(N, 128), H, B);
+    if constexpr (kIs16<T>) {
+        if (gd_knobs().attn_dma) {      // GD_ATTN_DMA=0: the register-staged forward kernel (A/B testing)
+            hipLaunchKernelGGL(attn_fwd_dma_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv, (T*)o, lse, N, H, scale, gd_knobs().attn_rot);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(attn_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv, (T*)o, lse, N, H, scale);
+}
+
 extern "C" int gd_attention_fwd(const void* qkv, void* o, float* lse, int B, int N, int H, int head_dim, float scale,
                                 int dtype, void* stream) {
     GD_REQUIRE(B > 0 && N > 0 && H > 0, "gd_attention_fwd: bad shape B=%d N=%d H=%d", B, N, H);
@@ -1674,85 +1106,83 @@ extern "C" int gd_attention_fwd(const void* qkv, void* o, float* lse, int B, int
     GD_REQUIRE((long)N * 3 * H * HD * 4 < (1L << 31), "gd_attention_fwd: one image's qkv rows must span < 2^31 bytes (32-bit tile offsets): N=%d H=%d", N, H);
     GD_REQUIRE(dtype == GD_F32 || dtype == GD_BF16 || dtype == GD_F32X3 || dtype == GD_F16, "gd_attention_fwd: bad dtype %d", dtype);
     GD_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)o & 15) == 0, "gd_attention_fwd: pointers must be 16-byte aligned");
-    dim3 grid(gd_cdiv(N, 128), H, B);
-    const int dma = gd_knobs().attn_dma;   // GD_ATTN_DMA=0: the register-staged forward kernel (A/B testing)
-    if (dtype == GD_BF16 && dma)
-        { const int ro = gd_knobs().attn_rot;
-          hipLaunchKernelGGL(attn_fwd_dma_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, (bf16*)o, lse, N, H, scale, ro); }
-    else if (dtype == GD_F16 && dma)        // tf32h engine: fp16 q / k / v / p (TF32's significand), the bf16 kernel's layouts
-        { const int ro = gd_knobs().attn_rot;
-          hipLaunchKernelGGL(attn_fwd_dma_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)qkv, (f16*)o, lse, N, H, scale, ro); }
-    else if (dtype == GD_F16)
-        hipLaunchKernelGGL(attn_fwd_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)qkv, (f16*)o, lse, N, H, scale);
-    else if (dtype == GD_BF16)
-        hipLaunchKernelGGL(attn_fwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, (bf16*)o, lse, N, H, scale);
-    else if (dtype == GD_F32X3)
-        hipLaunchKernelGGL(attn_fwd_kernel<x3>, grid, dim3(256), 0, (hipStream_t)stream, (const x3*)qkv, (x3*)o, lse, N, H, scale);
-    else
-        hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)qkv, (float*)o, lse, N, H, scale);
+    attn_with_type(dtype, [&](auto* t) { attn_fwd_launch<std::remove_pointer_t<decltype(t)>>(qkv, o, lse, B, N, H, scale, (hipStream_t)stream); });
     GD_LAUNCH_OK();
     return 0;
 }
 
-template <typename T>      // bf16 | f16
-static void attn_bwd_launch16(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, float* delta_ws, int B, int N, int H,
-                              float scale, int grad_order, bool no_dk, hipStream_t s) {
-    dim3 grid(gd_cdiv(N, 128), H, B);
-        if (gd_knobs().attn_dq_dma) hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv, (const T*)o, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale);
-        else
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv, (const T*)o, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale);
-        // 128-key blocks of four waves (two blocks per CU, independent barriers, Q / dO tiles staged twice as often) when the last
-        // 256-key block would be less than half full: N = 1370 pads to 1408 keys instead of 1536 (2.7 % instead of 10.8 %):
-        // backward 1574 -> 1514 us at 64 x 12 x 1370; at N = 6401 (long sweeps, 0.4 % vs 2 % padding) the 8-wave form is 2 % faster.
-        // GD_ATTN_DKV_NW = 4 | 8 forces one form.
-        const int dkv_env = gd_knobs().attn_dkv_nw;
-        const int tail = N % 256;
-        const int dkv_nw = dkv_env ? dkv_env : ((N < 4096 && tail > 0 && tail <= 128) ? 4 : 8);
-        const bool dkv_dma = gd_knobs().attn_dkv_dma != 0;      // GD_ATTN_DKV_DMA=0: the register-staged kernels (A/B)
-        if (no_dk && dkv_nw == 4 && dkv_dma)
-            hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<T, false>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const T*)qkv, (const T*)dout, delta_ws, (T*)dqkv, N, H, scale, grad_order);
-        else if (dkv_nw == 4 && dkv_dma)
-            hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<T, true>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const T*)qkv, (const T*)dout, delta_ws, (T*)dqkv, N, H, scale, grad_order);
-        else if (no_dk && dkv_nw == 4)
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale, grad_order);
-        else if (no_dk)
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false>), dim3(gd_cdiv(N, 256), H, B), dim3(512), 0, s, (const T*)qkv, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale, grad_order);
-        else if (dkv_nw == 4)       // (two-wave 64-key blocks: 2213 us — the staging registers spill and every block re-stages all of Q / dO)
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale, grad_order);
-        else
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8>), dim3(gd_cdiv(N, 256), H, B), dim3(512), 0, s, (const T*)qkv, (const T*)dout, lse, delta_ws, (T*)dqkv, N, H, scale, grad_order);
+// Which dK/dV kernel runs: 32 keys per wave, `waves` waves per block (4 | 8); `dma`: the four-wave LDS-DMA kernel (16-bit operands only).
+struct DkvForm { int waves; bool dma; };
+// opt_nw = GD_ATTN_DKV_NW (0 auto | 4 | 8: forces one form), opt_dma = GD_ATTN_DKV_DMA (0: the register-staged kernels, A/B).
+static DkvForm attn_dkv_form(int dtype, int N, int opt_nw, int opt_dma) {
+    if (dtype == GD_F32) return {8, false};
+    if (dtype == GD_F32X3) return {4, false};      // the whole register file per wave (the (hi, lo) fragments double the operand registers)
+    // 16-bit: 128-key blocks of four waves (two blocks per CU, independent barriers, Q / dO tiles staged twice as often) when the last
+    // 256-key block would be less than half full: N = 1370 pads to 1408 keys instead of 1536 (2.7 % instead of 10.8 %):
+    // backward 1574 -> 1514 us at 64 x 12 x 1370; at N = 6401 (long sweeps, 0.4 % vs 2 % padding) the 8-wave form is 2 % faster.
+    // (two-wave 64-key blocks: 2213 us — the staging registers spill and every block re-stages all of Q / dO)
+    const int tail = N % 256;
+    const int waves = opt_nw ? opt_nw : ((N < 4096 && tail > 0 && tail <= 128) ? 4 : 8);
+    return {waves, waves == 4 && opt_dma != 0};
+}
+
+struct AttnBwdArgs {
+    const void *qkv, *o, *dout;
+    const float* lse;
+    void* dqkv;
+    float* ws;
+    int B, N, H;
+    float scale;
+    int vfirst;
+    hipStream_t s;
+};
+template <typename T, int NW, bool DK> static void attn_dkv_launch_regs(const AttnBwdArgs& a) {
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, NW, DK>), dim3(gd_cdiv(a.N, 32 * NW), a.H, a.B), dim3(64 * NW), 0, a.s, (const T*)a.qkv, (const T*)a.dout, a.lse,
+                       a.ws, (T*)a.dqkv, a.N, a.H, a.scale, a.vfirst);
+}
+// (only the forms attn_dkv_form can return for T are instantiated)
+template <typename T, bool DK> static void attn_dkv_launch(const AttnBwdArgs& a, DkvForm f) {
+    if constexpr (kIs16<T>) {
+        if (f.dma) {
+            hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<T, DK>), dim3(gd_cdiv(a.N, 128), a.H, a.B), dim3(256), 0, a.s, (const T*)a.qkv, (const T*)a.dout, a.ws,
+                               (T*)a.dqkv, a.N, a.H, a.scale, a.vfirst);
+            return;
+        }
+    }
+    if constexpr (std::is_same<T, float>::value) attn_dkv_launch_regs<T, 8, DK>(a);
+    else if constexpr (IsX3<T>::v) attn_dkv_launch_regs<T, 4, DK>(a);
+    else if (f.waves == 4) attn_dkv_launch_regs<T, 4, DK>(a);
+    else attn_dkv_launch_regs<T, 8, DK>(a);
+}
+template <typename T> static void attn_bwd_launch(const AttnBwdArgs& a, DkvForm f, bool no_dk) {
+    const dim3 grid(gd_cdiv(a.N, 128), a.H, a.B);
+    bool dq_dma = false;
+    if constexpr (kIs16<T>) {
+        dq_dma = gd_knobs().attn_dq_dma != 0;      // GD_ATTN_DQ_DMA=0: the register-staged kernel (A/B)
+        if (dq_dma) hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<T>, grid, dim3(256), 0, a.s, (const T*)a.qkv, (const T*)a.o, (const T*)a.dout, a.lse, a.ws, (T*)a.dqkv, a.N, a.H, a.scale);
+    }
+    if (!dq_dma) hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, grid, dim3(256), 0, a.s, (const T*)a.qkv, (const T*)a.o, (const T*)a.dout, a.lse, a.ws, (T*)a.dqkv, a.N, a.H, a.scale);
+    // the exact-f32 kernel has no dV-only form: it computes dK whether or not it is needed
+    if constexpr (std::is_same<T, float>::value) attn_dkv_launch<T, true>(a, f);
+    else if (no_dk) attn_dkv_launch<T, false>(a, f);
+    else attn_dkv_launch<T, true>(a, f);
 }
 
 extern "C" int gd_attention_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
                                 float* delta_ws, int B, int N, int H, int head_dim, float scale, int dtype,
                                 int grad_order, void* stream) {
     GD_REQUIRE(grad_order >= 0 && grad_order <= 3, "gd_attention_bwd: grad_order bit 0: 0 = (dq, dk, dv), 1 = (dq, dv, dk); bit 1: dK not needed");
-    const bool no_dk = (grad_order & 2) != 0;
-    grad_order &= 1;
     GD_REQUIRE(B > 0 && N > 0 && H > 0, "gd_attention_bwd: bad shape B=%d N=%d H=%d", B, N, H);
     GD_REQUIRE(head_dim == HD, "gd_attention_bwd: head_dim must be 64 (got %d)", head_dim);
     GD_REQUIRE((long)N * 3 * H * HD * 4 < (1L << 31), "gd_attention_bwd: one image's qkv rows must span < 2^31 bytes (32-bit tile offsets): N=%d H=%d", N, H);
     GD_REQUIRE(dtype == GD_F32 || dtype == GD_BF16 || dtype == GD_F32X3 || dtype == GD_F16, "gd_attention_bwd: bad dtype %d", dtype);
     GD_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)dqkv & 15) == 0,
                "gd_attention_bwd: pointers must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
     GD_REQUIRE(((uintptr_t)o & 15) == 0, "gd_attention_bwd: o must be 16-byte aligned");
-    dim3 grid(gd_cdiv(N, 128), H, B);
-    if (dtype == GD_BF16) {
-        attn_bwd_launch16<bf16>(qkv, o, dout, lse, dqkv, delta_ws, B, N, H, scale, grad_order, no_dk, s);
-    } else if (dtype == GD_F16) {      // tf32h engine: dout arrives times a power of two (the caller's gd_amax_scale), dqkv leaves with it
-        attn_bwd_launch16<f16>(qkv, o, dout, lse, dqkv, delta_ws, B, N, H, scale, grad_order, no_dk, s);
-    } else if (dtype == GD_F32X3) {
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<x3>, grid, dim3(256), 0, s, (const x3*)qkv, (const x3*)o, (const x3*)dout, lse, delta_ws, (x3*)dqkv, N, H, scale);
-        // four-wave 128-key blocks with the whole register file per wave (the (hi, lo) fragments double the operand registers)
-        if (no_dk)
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<x3, 4, false>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const x3*)qkv, (const x3*)dout, lse, delta_ws, (x3*)dqkv, N, H, scale, grad_order);
-        else
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<x3, 4>), dim3(gd_cdiv(N, 128), H, B), dim3(256), 0, s, (const x3*)qkv, (const x3*)dout, lse, delta_ws, (x3*)dqkv, N, H, scale, grad_order);
-    } else {
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, grid, dim3(256), 0, s, (const float*)qkv, (const float*)o, (const float*)dout, lse, delta_ws, (float*)dqkv, N, H, scale);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<float, 8>), dim3(gd_cdiv(N, 256), H, B), dim3(512), 0, s, (const float*)qkv, (const float*)dout, lse, delta_ws, (float*)dqkv, N, H, scale, grad_order);
-    }
+    const AttnBwdArgs a = {qkv, o, dout, lse, dqkv, delta_ws, B, N, H, scale, grad_order & 1, (hipStream_t)stream};
+    const DkvForm f = attn_dkv_form(dtype, N, gd_knobs().attn_dkv_nw, gd_knobs().attn_dkv_dma);
+    const bool no_dk = (grad_order & 2) != 0;
+    attn_with_type(dtype, [&](auto* t) { attn_bwd_launch<std::remove_pointer_t<decltype(t)>>(a, f, no_dk); });
     GD_LAUNCH_OK();
     return 0;
 }

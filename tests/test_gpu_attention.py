@@ -148,3 +148,40 @@ def test_attention_reference_geometry_token_counts(dtype, tol, gtol, N):
     assert rel_err(o, ro) < tol and rel_err(lse, rl) < (1e-5 if dtype == torch.float32 else 1e-2) and rel_err(dqkv, rg) < gtol
 
 
+
+
+_ATTN_OPTION_DEFAULTS = {"attn_dma": 1, "attn_rot": 1, "attn_dq_dma": 1, "attn_dkv_dma": 1, "attn_dkv_nw": 0}
+
+
+@pytest.mark.parametrize("dtype,tol,gtol", [(torch.bfloat16, 2e-2, 3e-2), (torch.float16, 3e-3, 6e-3)])
+@pytest.mark.parametrize("B,N,H", [(1, 17, 1), (2, 200, 2), (1, 257, 3), (1, 512, 3), (2, 1370, 2)])
+def test_attention_option_only_paths(dtype, tol, gtol, B, N, H):
+    """The kernels that only an option reaches — the register-staged 16-bit forward / dQ / dK/dV (attn_dma, attn_dq_dma, attn_dkv_dma = 0), the
+    unrotated key order (attn_rot = 0) and a forced four- or eight-wave dK/dV form (attn_dkv_nw = 4 | 8) — one option off its default at a time,
+    against the fp64 reference with the tolerances of the default path (test_attention for bf16, test_attention_reference_geometry_token_counts for
+    fp16), plus the column-order and dV-only contracts.  The options change staging and summation order: equality with the default path is not
+    expected and not asserted."""
+    from gd_amd import ops
+    from gd_amd._lib import lib
+    g = torch.Generator(device="cuda").manual_seed(N)
+    qkv = torch.randn(B * N, 3 * H * 64, generator=g, device="cuda").to(dtype)
+    dout = torch.randn(B * N, H * 64, generator=g, device="cuda").to(dtype)
+    ro, rl, rg = _ref(qkv, B, N, H, dout)
+    D = H * 64
+    try:
+        for name, val in [("attn_dma", 0), ("attn_rot", 0), ("attn_dq_dma", 0), ("attn_dkv_dma", 0), ("attn_dkv_nw", 4), ("attn_dkv_nw", 8)]:
+            assert lib().gd_debug_set(name.encode(), val) == 0
+            o, lse = ops.attention_fwd(qkv, B, N, H)
+            dqkv = ops.attention_bwd(qkv, o, dout, lse, B, N, H)
+            d2 = ops.attention_bwd(qkv, o, dout, lse, B, N, H, vfirst=True)
+            d3 = ops.attention_bwd(qkv, o, dout, lse, B, N, H, vfirst=True, need_dk=False)
+            assert lib().gd_debug_set(name.encode(), _ATTN_OPTION_DEFAULTS[name]) == 0
+            errs = (rel_err(o, ro), rel_err(lse, rl), rel_err(dqkv, rg))
+            print(f"{name}={val} {dtype} B={B} N={N} H={H}: o {errs[0]:.3e} lse {errs[1]:.3e} dqkv {errs[2]:.3e}")
+            assert errs[0] < tol and errs[1] < 1e-2 and errs[2] < gtol, (name, val, errs)
+            assert torch.equal(d2[:, :D], dqkv[:, :D]) and torch.equal(d2[:, D:2 * D], dqkv[:, 2 * D:]) and \
+                torch.equal(d2[:, 2 * D:], dqkv[:, D:2 * D]), (name, val)
+            assert torch.equal(d3[:, :2 * D], d2[:, :2 * D]), (name, val)
+    finally:
+        for name, val in _ATTN_OPTION_DEFAULTS.items():
+            lib().gd_debug_set(name.encode(), val)
