@@ -146,6 +146,11 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "gd_transfer_argmax_workspace_bytes": (c_size_t, [c_int]),
     "gd_transfer_argmax": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gd_track_row_norms": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "gd_track_points_workspace_bytes": (c_size_t, [c_int]),
+    "gd_track_points": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     "gd_point_cloud_to_depth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_post_process_depth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gd_post_process_depth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float,

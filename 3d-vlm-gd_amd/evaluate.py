@@ -1,9 +1,9 @@
-"""Correspondence evaluation of a fine-tuned backbone: the two methods the reference's EvaluationCallback runs every 10 epochs
-(src/evaluate_timm.py:591-730) — semantic keypoint transfer (:461-588) and the OnePose++ descriptor matching (:140-179) — with
-the features on the HIP forward and the matching on gd_match_argmax / gd_transfer_argmax.  Everything runs under
-torch.no_grad(); nothing here touches the training step's caches (FinetuneGD._forward / _kp_pair are keyed by data_ptr and
-belong to the step).  Dataset readers, the random template subsample and PnP (cv2) stay with the caller; TAP-Vid tracking is
-not covered.
+"""Correspondence evaluation of a fine-tuned backbone: the three methods the reference's EvaluationCallback runs every 10 epochs
+(src/evaluate_timm.py:591-730) — semantic keypoint transfer (:461-588), the OnePose++ descriptor matching (:140-179) and TAP-Vid
+tracking (:234-348) — with the features on the HIP forward, the matching on gd_match_argmax / gd_transfer_argmax and the tracker
+head on gd_track_points.  Everything runs under torch.no_grad(); nothing here touches the training step's caches
+(FinetuneGD._forward / _kp_pair are keyed by data_ptr and belong to the step).  Dataset readers, image decoding and resizing, the
+random template subsample and PnP (cv2) stay with the caller.
 
 The reference's own quirks are kept, because the numbers it reports depend on them:
   - the query keypoints of the transfer are sampled with interpolate_features' DEFAULT mapping (patch 14, stride 14) on the
@@ -200,3 +200,227 @@ def semantic_transfer_pck(module, pairs, img_size=640, alphas=(0.10, 0.05, 0.15)
     out = {f"PCK{a:.2f}": float(v) for a, v in zip(alphas, res.tolist())}
     out["n"] = int(sum(len(g) for g in gts))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- TAP-Vid tracking
+# src/evaluate_timm.py:234-348 (tracking_single / tracking) on utils/tracking_model.py (Tracker, ModelInference) and
+# utils/tracking_metrics.py.  Defaults: patch 16, stride patch // 2, radius 35, anchor cosine 0.7, visibility cosine 0.6.
+def track_geometry(img_h, img_w, patch, stride, pitch=None):
+    """(img_h, img_w, patch, stride, gh, gw, pitch) of a tracking video: the grid is 1 + (img - patch) // stride per axis."""
+    gh, gw = token_grid(img_h, img_w, patch, stride)
+    return (int(img_h), int(img_w), int(patch), int(stride), gh, gw, gw if pitch is None else int(pitch))
+
+
+def grid_xy(geom):
+    """Pixel position of every cell of the gh x gw grid, raster order -> fp64 [gh * gw, 2] (x, y) = (col * s + p // 2, row * s + p // 2)
+    (TrackerHead.soft_argmax's gen_grid, tracking_model.py:151-156)."""
+    _, _, p, s, gh, gw, _ = geom
+    yy, xx = torch.meshgrid(torch.arange(gh, dtype=torch.float64), torch.arange(gw, dtype=torch.float64), indexing="ij")
+    return torch.stack([xx * s + p // 2, yy * s + p // 2], -1).reshape(-1, 2)
+
+
+def disc_cells(geom, radius, cell):
+    """Raster indices of the cells whose centre lies within `radius` pixels of cell `cell`'s (integer dx^2 + dy^2 <= r^2)."""
+    _, _, p, s, gh, gw, _ = geom
+    cy, cx = divmod(int(cell), gw)
+    out = []
+    for y in range(gh):
+        for x in range(gw):
+            if ((x - cx) * s) ** 2 + ((y - cy) * s) ** 2 <= radius * radius:
+                out.append(y * gw + x)
+    return out
+
+
+def lower_median(x, dim=0):
+    """torch.median's value along `dim`: for an even count the lower of the two middle values."""
+    return torch.sort(x, dim=dim).values.select(dim, (x.shape[dim] - 1) // 2)
+
+
+def video_token_maps(module, frames, stride=None, chunk=8):
+    """Dense per-frame token maps for tracking (src/evaluate_timm.py:259-282): the patch stride is overridden to `stride` (default
+    patch // 2) for this call only, frames [T, 3, H, W] CUDA fp32 in [0, 1] run through `token_maps` in chunks of `chunk`.
+    -> (fmap [T, gh * pitch, D] fp32, gh, gw, pitch)."""
+    m, P, st0 = _backbone(module)
+    s = P // 2 if stride is None else int(stride)
+    frames = _image(frames)
+    old = m.patch_embed.proj.stride
+    m.patch_embed.proj.stride = (s, s)
+    try:
+        maps, geo = [], None
+        for i in range(0, frames.shape[0], max(1, int(chunk))):
+            fm, gh, gw, pitch = token_maps(module, frames[i:i + chunk])
+            maps.append(fm.float().contiguous())
+            geo = (gh, gw, pitch)
+        return (torch.cat(maps) if len(maps) > 1 else maps[0]), geo[0], geo[1], geo[2]
+    finally:
+        m.patch_embed.proj.stride = old
+
+
+def _sample_frames(fmap, geom, pts, frames):
+    """Bilinear samples (grid_sample align_corners=True, border; the (patch, stride) mapping of normalize_points_for_sampling) of
+    fmap at pts [R, 2] in frame frames[R] -> [R, D] fp32, rows in input order."""
+    img_h, img_w, p, s, gh, gw, pitch = geom
+    R = pts.shape[0]
+    out = torch.empty(R, fmap.shape[-1], dtype=torch.float32, device=fmap.device)
+    fr = frames.cpu()
+    for t in torch.unique(fr).tolist():
+        idx = (fr == t).nonzero().reshape(-1).to(fmap.device)
+        out[idx] = _sample(fmap[t:t + 1], pts.index_select(0, idx)[None], gh, gw, pitch, img_h, img_w, p, s)[0]
+    return out
+
+
+def track_queries(fmap, geom, query_points, *, radius=35, anchor_cos=0.7, cos_th=0.6, precision="f16", want_occlusion=True,
+                  features=None):
+    """ModelInference.infer (utils/tracking_model.py:578-594, batch_size=None) on gd_track_points.
+    fmap [T, gh * pitch, D] (video_token_maps), geom = track_geometry(...), query_points [N, 3] (x, y, t) in pixels of the frames.
+    -> (tracks [N, T, 2] fp32 (x, y), occluded [N, T] bool).  `features`: a prepared ops.TrackFeatures of fmap (reused across calls).
+    Raises GdHipError for a query whose anchor set is empty (where the reference's torch.median of an empty tensor fails)."""
+    with torch.no_grad():
+        T = fmap.shape[0]
+        dev = fmap.device
+        tf = features if features is not None else ops.TrackFeatures(fmap, precision)
+        q = query_points.to(dev, torch.float32).reshape(-1, 3)
+        N = q.shape[0]
+        tq = q[:, 2].round().long()
+        if N == 0:
+            return torch.empty(0, T, 2, device=dev), torch.zeros(0, T, dtype=torch.bool, device=dev)
+        if int(tq.min()) < 0 or int(tq.max()) >= T:
+            raise GdHipError(f"track_queries: query frames must lie in [0, {T})")
+        # step 4: the query embedding against every frame
+        emb = _sample_frames(fmap, geom, q[:, :2].contiguous(), tq)                               # [N, D]
+        tiles = []
+        for t in range(T):
+            for r0 in range(0, N, 128):
+                tiles.append([t, r0, min(128, N - r0), t * N + r0])
+        traj = ops.track_points(emb, tf, geometry=geom, radius=radius, precision=precision, tiles=tiles).view(T, N, 2)
+        tracks = traj.transpose(0, 1).contiguous()                                               # [N, T, 2]
+        if not want_occlusion:
+            return tracks, torch.zeros(N, T, dtype=torch.bool, device=dev)
+        # step 5: samples along the trajectory, cosine against the trajectory's own point in the query frame
+        tframes = torch.arange(T, device=dev).repeat(N)
+        samp = _sample_frames(fmap, geom, tracks.reshape(-1, 2), tframes).view(N, T, -1)         # [N, T, D]
+        ref = samp[torch.arange(N, device=dev), tq.to(dev)]                                       # [N, D]
+        cos = torch.nn.functional.cosine_similarity(ref[:, None], samp, dim=-1, eps=1e-8)          # [N, T]
+        anchors = (cos >= anchor_cos).cpu()                                                       # the one host sync of the video
+        cnt = anchors.sum(1)
+        if int(cnt.min()) == 0:
+            bad = int((cnt == 0).nonzero()[0, 0])
+            raise GdHipError(f"track_queries: query {bad} ({query_points[bad].tolist()}) has no anchor frame (cos >= {anchor_cos})")
+        # step 6: every trajectory sample against every anchor frame, rows grouped by anchor frame into full tiles
+        nn_, aa = anchors.nonzero(as_tuple=True)                                                  # (query, anchor) pairs
+        rows = (nn_[:, None] * T + torch.arange(T)[None]).reshape(-1)                             # sample rows n*T + t
+        frames = aa[:, None].expand(-1, T).reshape(-1)
+        green = ops.track_points(samp.reshape(N * T, -1).index_select(0, rows.to(dev)), tf, frames=frames, geometry=geom,
+                                 radius=radius, precision=precision).view(-1, T, 2)              # [pairs, T, 2]
+        # step 7: occlusion from the anchors' cycle distances
+        occ = torch.empty(N, T, dtype=torch.bool, device=dev)
+        start = 0
+        for n in range(N):
+            k = int(cnt[n])
+            a_idx = aa[start:start + k].to(dev)
+            d = torch.linalg.norm(green[start:start + k] - tracks[n, a_idx][:, None], dim=-1)     # [A, T]
+            med = lower_median(d, 0)                                                               # [T]
+            th = med[a_idx].max()
+            occ[n] = (med > th) | (cos[n] < cos_th)
+            start += k
+        return tracks, occ
+
+
+# ---- TAP-Vid metrics (utils/tracking_metrics.py:7-221), numpy ------------------------------------------------------------------
+def compute_tapvid_metrics(query_points, gt_occluded, gt_tracks, pred_occluded, pred_tracks, query_mode, get_trackwise_metrics=False):
+    """TAP-Vid metrics (occlusion accuracy, pts_within_{1,2,4,8,16}, jaccard_{...}, the two averages) on [b, n, ...] arrays in
+    256-scaled raster coordinates; query_points [b, n, 3] (t, y, x).  query_mode 'first' (frames after the query) or 'strided'
+    (every frame but the query's).  -> dict of arrays [b] (or [b, n] with get_trackwise_metrics)."""
+    import numpy as np
+    axes = (2,) if get_trackwise_metrics else (1, 2)
+    T = gt_tracks.shape[2]
+    eye = np.eye(T, dtype=np.int32)
+    if query_mode == "first":
+        evalf = np.cumsum(eye, axis=1) - eye
+    elif query_mode == "strided":
+        evalf = 1 - eye
+    else:
+        raise ValueError("Unknown query mode " + query_mode)
+    ev = evalf[np.round(query_points[..., 0]).astype(np.int32)] > 0
+    out = {"occlusion_accuracy": np.sum(np.equal(pred_occluded, gt_occluded) & ev, axis=axes) / np.sum(ev, axis=axes)}
+    vis, pvis = np.logical_not(gt_occluded), np.logical_not(pred_occluded)
+    fracs, jacs = [], []
+    for th in (1, 2, 4, 8, 16):
+        within = np.sum(np.square(pred_tracks - gt_tracks), axis=-1) < np.square(th)
+        correct = np.logical_and(within, vis)
+        n_vis = np.sum(vis & ev, axis=axes)
+        frac = np.sum(correct & ev, axis=axes) / n_vis
+        tp = np.sum(correct & pvis & ev, axis=axes)
+        fp = np.sum((((~vis) & pvis) | ((~within) & pvis)) & ev, axis=axes)
+        jac = tp / (n_vis + fp)
+        out[f"pts_within_{th}"], out[f"jaccard_{th}"] = frac, jac
+        fracs.append(frac)
+        jacs.append(jac)
+    out["average_jaccard"] = np.mean(np.stack(jacs, axis=1), axis=1)
+    out["average_pts_within_thresh"] = np.mean(np.stack(fracs, axis=1), axis=1)
+    return out
+
+
+def compute_tapvid_metrics_for_video(trajectories_dict, occlusions_dict, benchmark_data, video_idx, pred_video_sizes=None):
+    """utils/tracking_metrics.py:150-221: the per-query-frame predictions {frame: [n, T, 2]} / {frame: [n, T]} of one video against
+    its benchmark entry, scaled to 256 x 256 ('strided' queries) -> {metric: float}.  The reference's query-point rescale writes
+    column 1 from column 2 and then column 2 from the NEW column 1 (:203-204); only column 0 (the frame) is read afterwards, so
+    the quirk is kept and has no effect."""
+    import numpy as np
+    cfg = next(v for v in benchmark_data["videos"] if v["video_idx"] == video_idx)
+    rh = cfg["h"] if pred_video_sizes is None else pred_video_sizes[1]
+    rw = cfg["w"] if pred_video_sizes is None else pred_video_sizes[0]
+    qp, gto, gtt, po, pt = [], [], [], [], []
+    for f in cfg["query_points"]:
+        q = np.array(cfg["query_points"][f])
+        qp.append(np.concatenate([np.array([f] * q.shape[0])[:, None], q], axis=1))
+        gtt.append(cfg["target_points"][f])
+        gto.append(cfg["occluded"][f])
+        pt.append(trajectories_dict[f])
+        po.append(occlusions_dict[f])
+    qp = np.concatenate(qp, axis=0, dtype=np.float32)
+    gtt = np.concatenate(gtt, axis=0, dtype=np.float32)
+    gto = np.concatenate(gto, axis=0, dtype=object)
+    pt = np.concatenate(pt, axis=0, dtype=np.float32)
+    po = np.concatenate(po, axis=0, dtype=object)
+    qp[..., 1] = qp[..., 2] * 256 / cfg["h"]
+    qp[..., 2] = qp[..., 1] * 256 / cfg["w"]
+    gtt[..., 0] *= 256 / cfg["w"]
+    gtt[..., 1] *= 256 / cfg["h"]
+    pt[..., 0] *= 256 / rw
+    pt[..., 1] *= 256 / rh
+    m = compute_tapvid_metrics(qp[None], gto[None], gtt[None], po[None], pt[None], query_mode="strided")
+    return {k: v.item() for k, v in m.items()}
+
+
+def tapvid_video_metrics(module, frames, video_config, *, patch=None, stride=None, radius=35, anchor_cos=0.7, cos_th=0.6,
+                         precision="f16", chunk=8):
+    """tracking_single (src/evaluate_timm.py:234-335) on already-decoded frames [T, 3, H, W] (CUDA fp32 in [0, 1], resized by the
+    caller to H, W floored to multiples of the patch) and the video's benchmark dict (the strided-pkl entry: video_idx, h, w,
+    query_points, target_points, occluded).  -> {metric: float, ..., "video_idx": int}."""
+    _, P, _ = _backbone(module)
+    s = P // 2 if stride is None else int(stride)
+    H, W = frames.shape[-2:]
+    fmap, gh, gw, pitch = video_token_maps(module, frames, stride=s, chunk=chunk)
+    geom = (int(H), int(W), P if patch is None else int(patch), s, gh, gw, pitch)
+    tf = ops.TrackFeatures(fmap, precision)
+    fx, fy = W / video_config["w"], H / video_config["h"]
+    trajs, occs = {}, {}
+    for f in sorted(video_config["query_points"].keys()):
+        q = torch.tensor([[fx * p[0], fy * p[1], f] for p in video_config["query_points"][f]], dtype=torch.float32)
+        tr, oc = track_queries(fmap, geom, q, radius=radius, anchor_cos=anchor_cos, cos_th=cos_th, precision=precision,
+                               features=tf)
+        trajs[f], occs[f] = tr.cpu().numpy(), oc.cpu().numpy()
+    m = compute_tapvid_metrics_for_video(trajs, occs, {"videos": [video_config]}, video_config["video_idx"], pred_video_sizes=[W, H])
+    m["video_idx"] = int(video_config["video_idx"])
+    return m
+
+
+def tracking(module, videos, **kw):
+    """tracking (src/evaluate_timm.py:338-348) over already-decoded videos [(frames, video_config), ...] -> (table: one metric dict per
+    video, mean: every metric's mean over the videos).  The reference's callback logs metrics_df.iloc[:, 1:].mean(), which drops the
+    first column (occlusion_accuracy); `mean` keeps every column."""
+    table = [tapvid_video_metrics(module, fr, cfg, **kw) for fr, cfg in videos]
+    keys = [k for k in table[0] if k != "video_idx"] if table else []
+    mean = {k: sum(r[k] for r in table) / len(table) for k in keys}
+    return table, mean

@@ -1398,3 +1398,109 @@ def transfer_argmax(S, img_hw, patch, stride, *, want_score=False):
     check(lib().gd_transfer_argmax(ptr(S), K, gh, gw, pitch, img_h, img_w, int(patch), int(stride), ptr(xy), ptr(sc), ptr(ws), stream()),
           "gd_transfer_argmax")
     return (xy, sc) if want_score else xy
+
+
+# ---------------------------------------------------------------------------------------------------------------- tracking evaluation
+def row_norms(x):
+    """||x_r|| fp32 for every row of a CUDA tensor [..., D] (fp32 / fp16 / bf16; gd_track_row_norms) -> [...] fp32."""
+    _req(x.is_cuda and x.dim() >= 1 and x.shape[-1] > 0, "row_norms: a CUDA tensor [..., D] with D > 0")
+    x = x.contiguous()
+    out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    rows = x.numel() // x.shape[-1]
+    if rows:
+        check(lib().gd_track_row_norms(ptr(x), rows, x.shape[-1], dtype_code(x), ptr(out), stream()), "gd_track_row_norms")
+    return out
+
+
+class TrackFeatures:
+    """A video's token grid prepared once for `track_points`: the fp32 (or input) features, their per-cell norms, and the MFMA operand
+    (for precision "f16": an fp16 copy of the fp32 grid under a power-of-two scale).  feats [T, gh * pitch, D] token-major."""
+
+    def __init__(self, feats, precision="f16"):
+        _req(precision in ("f32", "f16", "bf16"), f"track_points: precision must be 'f32', 'f16' or 'bf16', not {precision!r}")
+        _req(feats.is_cuda and feats.dim() == 3, "track_points: feats must be a CUDA tensor [T, gh * pitch, D]")
+        self.src = feats.contiguous()
+        self.precision = precision
+        self.T, self.ncell, self.D = self.src.shape
+        self.norms = row_norms(self.src)
+        self.op, self.inv = _track_operand(self.src, precision)
+
+
+def _track_operand(x, precision):
+    if precision == "f32":
+        _req(x.dtype == torch.float32, "track_points: precision 'f32' takes fp32 inputs")
+        return x, None
+    if precision == "bf16":
+        _req(x.dtype == torch.bfloat16, "track_points: precision 'bf16' takes bf16 inputs")
+        return x, None
+    _req(x.dtype in (torch.float32, torch.float16), "track_points: precision 'f16' takes fp32 or fp16 inputs")
+    if x.dtype == torch.float16:
+        return x, None
+    op, inv = _f16_operand(x.reshape(-1, x.shape[-1]))
+    return op.view(x.shape), inv
+
+
+def track_tiles(frames, max_rows=128):
+    """frame-per-row [R] int -> (order [R] int64: rows grouped by frame, stable; tiles int32 [n, 4] {frame, row0, nrows, out0}
+    over the ordered rows, at most max_rows rows each; out0 == row0).  Host tensors."""
+    f = torch.as_tensor(frames).to("cpu", torch.int64).reshape(-1)
+    order = torch.sort(f, stable=True).indices
+    fs = f[order].tolist()
+    tiles, i = [], 0
+    while i < len(fs):
+        j = i
+        while j < len(fs) and fs[j] == fs[i] and j - i < max_rows:
+            j += 1
+        tiles.append([fs[i], i, j - i, i])
+        i = j
+    return order, torch.tensor(tiles, dtype=torch.int32).reshape(-1, 4)
+
+
+def track_points(E, feats, frames=None, geometry=None, radius=35, precision="f16", want_cell=False, *, tiles=None):
+    """The tracker head (tracking_model.py:147-200 after the relu'd cosine map of :292-308) on gd_track_points.
+    E [R, D] embeddings (CUDA, fp32; bf16 for precision 'bf16'); feats [T, gh * pitch, D] or a TrackFeatures; frames [R] int: the
+    target frame of every row (rows are grouped by frame into tiles of up to 128), or tiles int [n, 4] {frame, row0, nrows, out0}
+    given directly; geometry = (img_h, img_w, patch, stride, gh, gw, pitch).  -> xy [R, 2] fp32 (pixels), and with want_cell the
+    argmax cell [R] int64 (raster index in the gh x gw grid)."""
+    tf = feats if isinstance(feats, TrackFeatures) else TrackFeatures(feats, precision)
+    _req(tf.precision == precision, f"track_points: features prepared for {tf.precision!r}, asked for {precision!r}")
+    _req(geometry is not None and len(geometry) == 7, "track_points: geometry = (img_h, img_w, patch, stride, gh, gw, pitch)")
+    img_h, img_w, patch, stride, gh, gw, pitch = (int(v) for v in geometry)
+    _req(E.is_cuda and E.dim() == 2 and E.shape[1] == tf.D, f"track_points: E must be a CUDA tensor [R, {tf.D}]")
+    _req(tf.ncell == gh * pitch, f"track_points: feats hold {tf.ncell} cells per frame, the geometry {gh} x {pitch}")
+    _req((frames is None) != (tiles is None), "track_points: give frames or tiles, not both")
+    R = E.shape[0]
+    dev = E.device
+    if tiles is None:
+        order, tl = track_tiles(frames)
+        _req(order.numel() == R, f"track_points: {order.numel()} frames for {R} rows")
+        if R == 0:
+            xy = torch.empty(0, 2, dtype=torch.float32, device=dev)
+            return (xy, torch.empty(0, dtype=torch.int64, device=dev)) if want_cell else xy
+        ident = bool(torch.equal(order, torch.arange(R)))
+        Eo = E if ident else E.index_select(0, order.to(dev))
+    else:
+        tl = torch.as_tensor(tiles).to("cpu", torch.int32).reshape(-1, 4)
+        ident, Eo = True, E
+    src = Eo.contiguous()
+    e_op, e_inv = _track_operand(src, precision)
+    e_norm = row_norms(src)
+    src_code = dtype_code(tf.src)
+    _req(dtype_code(src) == src_code, "track_points: E and feats must have the same dtype")
+    n_out = R if tiles is None else int((tl[:, 3].long() + tl[:, 2].long()).max())
+    xy = torch.empty(n_out, 2, dtype=torch.float32, device=dev)
+    cell = torch.empty(n_out, dtype=torch.int32, device=dev) if want_cell else None
+    tl = tl.contiguous()
+    ws = torch.empty(max(1, lib().gd_track_points_workspace_bytes(tl.shape[0])), dtype=torch.uint8, device=dev)
+    check(lib().gd_track_points(ptr(e_op), ptr(tf.op), ptr(src), ptr(tf.src), dtype_code(tf.op), src_code, src.shape[0], tf.T, gh, gw,
+                                pitch, tf.D, img_h, img_w, patch, stride, int(radius), ptr(e_norm), ptr(tf.norms), ptr(e_inv), ptr(tf.inv),
+                                tl.data_ptr(), tl.shape[0], n_out, ptr(xy), ptr(cell), ptr(ws), stream()), "gd_track_points")
+    if not ident:
+        out = torch.empty_like(xy)
+        out[order.to(dev)] = xy
+        xy = out
+        if want_cell:
+            c = torch.empty_like(cell)
+            c[order.to(dev)] = cell
+            cell = c
+    return (xy, cell.long()) if want_cell else xy

@@ -447,6 +447,27 @@ size_t gd_transfer_argmax_workspace_bytes(int K);
 int gd_transfer_argmax(const float* S, int K, int gh, int gw, int pitch, int img_h, int img_w, int patch, int stride,
                        long long* xy, float* score, void* workspace, void* stream);
 
+/* TAP-Vid tracking evaluation (src/evaluate_timm.py:234-348 `tracking_single` on utils/tracking_model.py).
+ * gd_track_row_norms: norms [rows] fp32 = ||X[r]|| of X [rows, D] (dtype GD_F32 / GD_F16 / GD_BF16), fp32 sums; replaces the
+ *   `frame_embeddings_set.norm(dim=1)` / `source_embeddings.norm(dim=1)` of tracking_model.py:296-298 (a video's cell norms are
+ *   computed once, not per call).
+ * gd_track_points: the tracker head (tracking_model.py:147-200 TrackerHead.forward / soft_argmax after the cosine map of
+ *   :292-308 and the relu of :307) for n_tiles host-side tiles {frame, row0, nrows <= 128, out0} (int [n_tiles][4]): for every
+ *   row e = E[row0 + i], c_g = e . F[frame][g] / max(|e| |F[frame][g]|, 1e-8) over the gh x gw cells (F [T][gh * pitch][D]
+ *   token-major, separator columns x >= gw skipped), r = relu(c), g* = first raster argmax of r (0 when every c <= 0), and
+ *   xy[out0 + i] = sum_{disc} (x_g, y_g) exp(r_g) / sum_{disc} exp(r_g) over the cells within `radius` pixels of g*
+ *   (x_g = col * stride + patch / 2, y_g = row * stride + patch / 2); cell[out0 + i] (nullable) = g*.  The disc's scores are
+ *   recomputed in fp32 from E_src / F_src: the operands themselves when dtype is GD_F32, else fp32 (src_dtype GD_F32) or the
+ *   operand dtype.  dtype GD_F16 is the tf32h class (per-tensor power-of-two scales, inv_scale_* device scalars, nullable = 1).
+ *   e_norm [E_rows], f_norm [T * gh * pitch]: gd_track_row_norms of E_src / F_src.  All arguments are checked before any HIP
+ *   call.  workspace: gd_track_points_workspace_bytes(n_tiles) bytes (it does not depend on the grid). */
+int gd_track_row_norms(const void* X, long rows, int D, int dtype, float* norms, void* stream);
+size_t gd_track_points_workspace_bytes(int n_tiles);
+int gd_track_points(const void* E, const void* F, const void* E_src, const void* F_src, int dtype, int src_dtype, long E_rows,
+                    int T, int gh, int gw, int pitch, int D, int img_h, int img_w, int patch, int stride, int radius,
+                    const float* e_norm, const float* f_norm, const float* inv_scale_e, const float* inv_scale_f,
+                    const int* tiles, int n_tiles, long n_out, float* xy, int* cell, void* workspace, void* stream);
+
 /* post_process_depth (utils/functions.py:262-345) on P rasterised depth maps [P,H,W]: max-pool closing, two hole-filling
  * passes, median (kernel_size in {3, 5}), bilateral, guided filter (guidance = the bilateral map, input = the median map, as the
  * call site passes them), 3-sigma outlier replacement, joint bilateral.  The four kornia filters are restated from kornia's
