@@ -16,7 +16,7 @@ MATCH_COLS = 1       # gd_match_argmax flags: also the column argmax (include/gd
 c_int, c_long, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 # name -> (restype, argtypes).  Must list every symbol of include/gd_hip.h (tests check this).
-ABI_VERSION = 3      # include/gd_hip.h GD_ABI_VERSION: the version this signature table was written for
+ABI_VERSION = 4      # include/gd_hip.h GD_ABI_VERSION: the version this signature table was written for
 SIGNATURES = {
     "gd_last_error": (ctypes.c_char_p, []),
     "gd_abi_version": (c_int, []),
@@ -87,7 +87,7 @@ SIGNATURES = {
     "gd_kp_gather_bwd": (c_int, [ctypes.POINTER(c_void_p), c_int, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_lora_bwd_fused": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gd_lora_bwd_fused_scaled": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "gd_lora_bwd_fused_scaled": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "gd_conv_weight_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gd_kp_patch_bwd_det": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                     c_float, c_int, c_int, c_int, c_int, c_void_p]),

@@ -20,6 +20,9 @@ struct LoraBwdParams {
     // in under the step's power-of-two scale s), dt and the gbt partial by *out_mul on the way out (1 / s: X or t carried s).  null = 1.
     const float* t_mul; const float* out_mul;
     int dt_scaled;                  // 1: dt leaves WITHOUT *out_mul (still in X's scaled domain: the consumers take it under s anyway)
+    // dt alone is also multiplied by dt_mul (host value, a power of two): bt arrives under 1 / dt_mul (LoRA B shifted out of fp16's subnormals:
+    // vit._opw_lora_b); B enters dt only, so gbt does not see it
+    float dt_mul;
 };
 
 #define LB_ROWS 64
@@ -51,6 +54,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int K = p.K;
     const T* X = (const T*)p.X;
     const float tmul = p.t_mul ? *p.t_mul : 1.0f, omul = p.out_mul ? *p.out_mul : 1.0f;
+    const float dtmul = p.dt_mul * (p.dt_scaled ? 1.0f : omul);      // (powers of two: exact)
     // the B factors stay in LDS for the whole launch
     const bool want_dt = p.bt != nullptr;          // bt == NULL: only gbt += t^T . X (e.g. the LoRA-A gradient dt^T . LN(x))
     if (want_dt)
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = chunk * LB_ROWS + 16 * wave + 4 * g + r;
-                if (m < p.M) p.dt[(long)m * 8 + c] = dacc[r] * (p.dt_scaled ? 1.0f : omul);
+                if (m < p.M) p.dt[(long)m * 8 + c] = dacc[r] * dtmul;
             }
         }
     }
@@ -175,16 +179,18 @@ extern "C" int gd_lora_bwd_fused(const void* dqv, long ldx, const float* t, cons
                                  void* stream) {
     GD_REQUIRE(M > 0 && K > 0 && K % LB_SLAB == 0 && K / LB_SLAB <= 8 && ldx % 8 == 0, "gd_lora_bwd_fused: K must be a multiple of 256 (<= 2048), ldx of 8");
     GD_REQUIRE(((uintptr_t)dqv & 15) == 0 && ((uintptr_t)bt & 15) == 0 && t && gbt && (dt || !bt), "gd_lora_bwd_fused: alignment / null pointers");
-    LoraBwdParams p = {dqv, ldx, t, bt, dt, gbt, M, K, nullptr, nullptr, 0};
+    LoraBwdParams p = {dqv, ldx, t, bt, dt, gbt, M, K, nullptr, nullptr, 0, 1.0f};
     return lora_bwd_launch<bf16>(p, (hipStream_t)stream);
 }
 
 // the same pass on either 16-bit operand type, with the tf32h engine's device-side scales (LoraBwdParams): dtype GD_BF16 | GD_F16
 extern "C" int gd_lora_bwd_fused_scaled(const void* dqv, long ldx, const float* t, const void* bt, float* dt, float* gbt, int M, int K, int dtype,
-                                        const float* t_mul_dev, const float* out_mul_dev, int dt_scaled, void* stream) {
+                                        const float* t_mul_dev, const float* out_mul_dev, int dt_scaled, float dt_mul, void* stream) {
     GD_REQUIRE(M > 0 && K > 0 && K % LB_SLAB == 0 && K / LB_SLAB <= 8 && ldx % 8 == 0, "gd_lora_bwd_fused_scaled: K must be a multiple of 256 (<= 2048), ldx of 8");
     GD_REQUIRE(((uintptr_t)dqv & 15) == 0 && ((uintptr_t)bt & 15) == 0 && t && gbt && (dt || !bt), "gd_lora_bwd_fused_scaled: alignment / null pointers");
     GD_REQUIRE(dtype == GD_BF16 || dtype == GD_F16, "gd_lora_bwd_fused_scaled: operands are bf16 or fp16 (dtype %d)", dtype);
-    LoraBwdParams p = {dqv, ldx, t, bt, dt, gbt, M, K, t_mul_dev, out_mul_dev, dt_scaled};
+    { int e; GD_REQUIRE(dt_mul > 0.f && dt_mul <= 1.0f && frexpf(dt_mul, &e) == 0.5f,
+                        "gd_lora_bwd_fused_scaled: dt_mul = %g is not a power of two in (0, 1] (it undoes bt's shift exactly)", (double)dt_mul); }
+    LoraBwdParams p = {dqv, ldx, t, bt, dt, gbt, M, K, t_mul_dev, out_mul_dev, dt_scaled, dt_mul};
     return dtype == GD_F16 ? lora_bwd_launch<f16>(p, (hipStream_t)stream) : lora_bwd_launch<bf16>(p, (hipStream_t)stream);
 }

@@ -762,15 +762,15 @@ def skinny_tn_mfma(t, x, out):
     return out
 
 
-def lora_bwd_fused_h(dqv, t, bt_qv, gbt, t_mul=None, out_mul=None, dt_scaled=False):
+def lora_bwd_fused_h(dqv, t, bt_qv, gbt, t_mul=None, out_mul=None, dt_scaled=False, dt_mul=1.0):
     """The fused LoRA backward on fp16 operands (tf32h engine): dqv [M, K] fp16 view, t [M, 8] f32, bt_qv [8, K] fp16 or None (then only
     gbt [8, K] f32 += (t * t_mul)^T . dqv * out_mul), t_mul / out_mul: one-element device tensors (the step's gradient scale s and 1 / s) or None
-    -> dt [M, 8] f32 = dqv . bt_qv^T * out_mul (None without bt_qv); dt_scaled: dt without out_mul (still in dqv's scaled domain).
-    gd_lora_bwd_fused_scaled."""
+    -> dt [M, 8] f32 = dqv . bt_qv^T * out_mul * dt_mul (None without bt_qv); dt_scaled: dt without out_mul (still in dqv's scaled domain).
+    dt_mul (host power of two): undoes the shift bt_qv was formatted under (vit._opw_lora_b) on dt alone.  gd_lora_bwd_fused_scaled."""
     M, K = dqv.shape
     dt = torch.empty(M, 8, dtype=torch.float32, device=dqv.device) if bt_qv is not None else None
     check(lib().gd_lora_bwd_fused_scaled(ptr(dqv), dqv.stride(0), ptr(t), ptr(bt_qv), ptr(dt), ptr(gbt), M, K, dtype_code(dqv), ptr(t_mul), ptr(out_mul),
-                                         1 if dt_scaled else 0, stream()), "gd_lora_bwd_fused_scaled")
+                                         1 if dt_scaled else 0, float(dt_mul), stream()), "gd_lora_bwd_fused_scaled")
     return dt
 
 

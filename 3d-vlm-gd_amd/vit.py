@@ -44,12 +44,15 @@ def _opw(w, fmt):
 
 
 LORA_B_SHIFT = 12
+LORA_DT_TARGET = 4096.0      # the fp16 LoRA-A gradient: max |dt| is carried to (2^11, 2^12] (see _BlockFn.backward)
 
 
 def _opw_lora_b(b):
     """LoRA B (f32 [2r, *]) as the fp16 right operand of the tf32h backward's dt product -> (operand, the host alpha that undoes its scale).
     B starts at zero and moves by ~lr per step: cast as it is, it would sit among fp16's subnormals (3e-3 relative at 1e-5).  Times 2^12 it keeps
-    11 bits from 2^-26 up to |B| = 16 (past that it saturates); the product takes alpha = 2^-12 (both powers of two: exact)."""
+    11 bits from 2^-26 up to |B| = 16 (past that it saturates); the product takes alpha = 2^-12 (both powers of two: exact).  Every consumer of a
+    formatted B in the backward goes through here: the skinny gemm_nt (alpha) and the fused one-pass kernel (ops.lora_bwd_fused_h(dt_mul=)),
+    per block or batched over the blocks (prepare_trainables)."""
     return ops.cast16(b, scale=2.0 ** LORA_B_SHIFT), 2.0 ** -LORA_B_SHIFT
 
 
@@ -391,11 +394,18 @@ class _BlockFn(torch.autograd.Function):
                 # then the LoRA-A gradient dt^T . LN(x) on the same kernel with dt going in under s
                 # (dt stays in the scaled domain with h16dy: both of its consumers — the LoRA-A gradient and the rank update of the dX GEMM —
                 #  take it under s)
-                bt16 = tw["bt_qv_w3"] if tw is not None and "bt_qv_w3" in tw and tw["bt_qv_w3"].dtype == torch.float16 else ops.cast16(bt_qv.float().contiguous())
-                dt = ops.lora_bwd_fused_h(dqv, t, bt16, z_bt, out_mul=sc[1:2], dt_scaled=h16dy)
+                # (B goes in times 2^LORA_B_SHIFT and dt alone comes out times 2^-LORA_B_SHIFT: _opw_lora_b; gbt and both consumers of dt never see it)
+                bt16, dtm = (tw["bt_qv_w3"], tw["bt_qv_mul"]) if tw is not None and "bt_qv_w3" in tw and tw["bt_qv_w3"].dtype == torch.float16 \
+                    else _opw_lora_b(bt_qv.float().contiguous())
+                dt = ops.lora_bwd_fused_h(dqv, t, bt16, z_bt, out_mul=sc[1:2], dt_scaled=h16dy, dt_mul=dtm)
                 gbt = z_bt
                 if ops.lora_bwd_fused_h_supported(y1, dt, None, z_at):
-                    ops.lora_bwd_fused_h(y1, dt, None, z_at, t_mul=None if h16dy else sc[0:1], out_mul=sc[1:2])
+                    # dt enters as an fp16 high + low pair and is ~|B| |dqv|: while B is still near its zero start that is far inside fp16's
+                    # subnormals in EITHER domain (|B| = 1e-6: dt s ~ 1e-5, spacing 6e-8), whatever the block's s.  So dt goes in under a power
+                    # of two of its own, taken from its maximum on the device (max |dt| -> (2^11, 2^12]: 2^4 below fp16's largest, and every
+                    # element down to 2^-26 of the maximum keeps 11 bits in the high part), and the result takes its inverse (h16dy: times 1 / s)
+                    sd = ops.amax_scale(dt, LORA_DT_TARGET)
+                    ops.lora_bwd_fused_h(y1, dt, None, z_at, t_mul=sd[0:1], out_mul=sd[1:2] * sc[1:2] if h16dy else sd[1:2])
                 else:       # (D not a multiple of 256, e.g. ViT-S: the streaming N = 8 kernel, fp32 dt against the fp16 LN(x))
                     ops.gemm_tn(dt, y1, out=z_at, alpha_dev=sc[1:2] if h16dy else None)
                 gat = z_at
@@ -741,8 +751,11 @@ class GDViT(nn.Module):
                 for i, w in enumerate(w3(at.float())):
                     extra[i]["at_w3"] = w
                 if self.opfmt == "h":      # (only the fp16-operand LoRA backward reads a formatted B: the tf32x one takes the plain tensors)
-                    for i, w in enumerate(w3(bt_qv.float())):
-                        extra[i]["bt_qv_w3"] = w
+                    # (under the power-of-two shift of _opw_lora_b: the fused backward undoes it on dt)
+                    # (the multiplier travels with the operand: the consumer never assumes a shift of its own)
+                    bw, bmul = _opw_lora_b(bt_qv.float().reshape(-1, 2 * D))
+                    for i, w in enumerate(bw.view(L, 2 * r, -1)):
+                        extra[i]["bt_qv_w3"], extra[i]["bt_qv_mul"] = w, bmul
         for i, (inner, _, _) in enumerate(lo):
             inner._tw = {"dtype": T, "at": at[i], "bt": bt[i], "at_T": at_T[i], "bt_T": bt_T[i], "bt_qv": bt_qv[i], "down_T": down_T[i],
                          "up_T": up_T[i], "down_tT": down_tT[i], "up_tT": up_tT[i], **extra[i]}

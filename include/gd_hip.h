@@ -27,9 +27,9 @@ extern "C" {
 const char* gd_last_error(void);
 /* Bumped whenever the exported surface changes (round 4: gd_amax_scale and gd_lora_bwd_fused_scaled took one more argument -> 2; round 6: the
  * entry points of five shelved experiments — gd_gemm_nt_lnfold_emit / _apply, gd_ln_fold_stats, gd_stream_create_cu_mask, gd_stream_destroy — left the
- * library, and round 5's gd_adapter_fused_h_ln / gd_kp_gather_fwd_ln are counted -> 3); the Python loader refuses a library whose version differs
+ * library, and round 5's gd_adapter_fused_h_ln / gd_kp_gather_fwd_ln are counted -> 3; gd_lora_bwd_fused_scaled took dt_mul -> 4); the Python loader refuses a library whose version differs
  * from the one its signature table was written for. */
-#define GD_ABI_VERSION 3
+#define GD_ABI_VERSION 4
 int gd_abi_version(void);
 
 /* Debug hooks (no reference counterpart; NOT for production use, process-wide, not thread-safe).
@@ -84,9 +84,11 @@ int gd_lora_bwd_fused(const void* dqv, long ldx, const float* t, const void* bt,
 /* The same pass (autograd of _LoRA_qkv, utils/model.py:57-71) on either 16-bit operand type (dtype GD_BF16 | GD_F16) with the tf32h engine's device-side scales: t is multiplied by *t_mul_dev
  * before it is split into its high and low 16-bit parts (a GRADIENT in the t role goes in under the step's power-of-two scale), dt and the gbt
  * partial by *out_mul_dev on the way out (1 / s when dqv or t carried s).  NULL = 1.  dt_scaled = 1: dt leaves WITHOUT *out_mul_dev — still
- * in dqv's scaled domain, for consumers that take it under s anyway (the LoRA rank update of a scaled-domain dX GEMM, the LoRA-A gradient). */
+ * in dqv's scaled domain, for consumers that take it under s anyway (the LoRA rank update of a scaled-domain dX GEMM, the LoRA-A gradient).
+ * dt_mul (ABI version 4; host value, a power of two in (0, 1]) multiplies dt alone, in either form: bt may arrive times 1 / dt_mul — LoRA B starts at
+ * zero and moves by ~1e-5 per step, which as fp16 is a subnormal; times 2^12 it keeps its 11 bits — and dt leaves without that factor; gbt never sees it. */
 int gd_lora_bwd_fused_scaled(const void* dqv, long ldx, const float* t, const void* bt, float* dt, float* gbt, int M, int K, int dtype,
-                             const float* t_mul_dev, const float* out_mul_dev, int dt_scaled, void* stream);
+                             const float* t_mul_dev, const float* out_mul_dev, int dt_scaled, float dt_mul, void* stream);
 
 /* Dense cost-volume KL for P pairs, fused: calculate_cost_loss (src/finetune_timm_vggt.py:488-533 variant 0,
  * src/finetune_timm_mast3r.py:504-540 variant 1) = F.normalize + bmm x2 + softmax + get_masked_patch_cost
