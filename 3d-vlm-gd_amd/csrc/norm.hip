@@ -335,6 +335,7 @@ extern "C" int gd_layernorm_fwd(const void* x, const float* gamma, const float* 
 #define F_BB(NV) hipLaunchKernelGGL((ln_fwd_kernel<bf16, bf16, NV>), grid, blk, 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, M, D, ldx, ldy, eps)
 #define F_BF(NV) hipLaunchKernelGGL((ln_fwd_kernel<bf16, float, NV>), grid, blk, 0, s, (const bf16*)x, gamma, beta, (float*)y, mean, rstd, M, D, ldx, ldy, eps)
 #define F_FF(NV) hipLaunchKernelGGL((ln_fwd_kernel<float, float, NV>), grid, blk, 0, s, (const float*)x, gamma, beta, (float*)y, mean, rstd, M, D, ldx, ldy, eps)
+#define F_FB(NV) hipLaunchKernelGGL((ln_fwd_kernel<float, bf16, NV>), grid, blk, 0, s, (const float*)x, gamma, beta, (bf16*)y, mean, rstd, M, D, ldx, ldy, eps)
 #define F_FH(NV) hipLaunchKernelGGL((ln_fwd_kernel<float, f16, NV>), grid, blk, 0, s, (const float*)x, gamma, beta, (f16*)y, mean, rstd, M, D, ldx, ldy, eps)
     const int ln16 = gd_knobs().ln_16b;
     const bool wide = ln16 && dtype == GD_BF16 && y_dtype == GD_BF16 && D % 8 == 0 && D <= 1024 && ldx % 8 == 0 && ldy % 8 == 0 &&
@@ -344,6 +345,7 @@ extern "C" int gd_layernorm_fwd(const void* x, const float* gamma, const float* 
     else if (dtype == GD_BF16 && y_dtype == GD_BF16) LN_DISPATCH_NV(D, F_BB);
     else if (dtype == GD_BF16 && y_dtype == GD_F32) LN_DISPATCH_NV(D, F_BF);
     else if (dtype == GD_F32 && y_dtype == GD_F32) LN_DISPATCH_NV(D, F_FF);
+    else if (dtype == GD_F32 && y_dtype == GD_BF16) LN_DISPATCH_NV(D, F_FB);     // fp32 residual stream, bf16 product operand (teacher blocks)
     else if (dtype == GD_F32 && y_dtype == GD_F16) LN_DISPATCH_NV(D, F_FH);      // tf32h engine: LN(x) is only ever a product operand
     else {
         gd_set_error("gd_layernorm_fwd: unsupported dtype pair %d -> %d", dtype, y_dtype);

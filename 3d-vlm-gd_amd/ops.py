@@ -498,6 +498,22 @@ def attention_bwd(qkv, o, dout, lse, B, N, H, vfirst=False, need_dk=True, x3=Fal
     return dqkv
 
 
+def qk_norm_rope(qkv, B, N, H, pos, gq, bq, gk, bk, eps, base, want_qk=False):
+    """In place on the packed qkv [B*N, 3*H*64] (f32 | bf16): q <- RoPE2D(LN_64(q; gq, bq, eps), pos), k likewise with gk, bk; v untouched
+    (vggt/layers/attention.py:58-65).  pos int64 [B*N, 2] (y, x); gq = bq = gk = bk = None: no normalisation.  want_qk: also returns
+    (q, k) as [B, H, N, 64], the layout teacher_glue.cross_view_attention_maps takes; otherwise None."""
+    _req(qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * N, 3 * H * 64), "qk_norm_rope: qkv must be a contiguous CUDA [B*N, 3*H*64]")
+    _req(pos.is_cuda and pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == B * N * 2, "qk_norm_rope: pos must be contiguous int64 [B*N, 2]")
+    for t in (gq, bq, gk, bk):
+        _req(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 64), "qk_norm_rope: gamma / beta must be fp32 [64]")
+    q_out = torch.empty(B, H, N, 64, dtype=qkv.dtype, device=qkv.device) if want_qk else None
+    k_out = torch.empty_like(q_out) if want_qk else None
+    rc = lib().gd_qk_norm_rope(ptr(qkv), ptr(pos), ptr(gq), ptr(bq), ptr(gk), ptr(bk), ptr(q_out), ptr(k_out), B, N, H, 64, float(eps), float(base),
+                               dtype_code(qkv), stream())
+    check(rc, "gd_qk_norm_rope")
+    return (q_out, k_out) if want_qk else None
+
+
 # ----------------------------------------------------------------------------------------------
 # views of the two halves of a [2P, ...] batch (view 1 / view 2 of P pairs)
 # ----------------------------------------------------------------------------------------------

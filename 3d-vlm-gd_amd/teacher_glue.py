@@ -233,16 +233,20 @@ def _border_ok(kp, h, w):
 
 
 def extract_vggt_targets(global_qk, depth_map, point_conf, extrinsic, intrinsic, track_fn, scale=64 ** -0.5, temperature=1.0,
-                         prefix=5, num_keypoints=300, min_distance=5, generator=None):
+                         prefix=5, num_keypoints=300, min_distance=5, generator=None, maps=None):
     """`extract_vggt_features` + `sample_keypoints` (src/finetune_timm_vggt.py:357-449) after the teacher forward.
     global_qk : list over the selected global-attention blocks of (q, k), each [1, H, N, 64] after q/k-norm and RoPE, N = the
                 two frames' tokens (the aggregator's `return_attn` blocks, vggt/models/aggregator.py:273)
     depth_map [2, H, W(,1)], point_conf [2, H, W], extrinsic [2, 3, 4], intrinsic [2, 3, 3]: the depth / camera heads' outputs
     track_fn  : kp_1 int [N, 2] (x, y) -> kp_2 [N, 2] — the teacher's track head (finetune_timm_vggt.py:439-440)
+    maps      : the finished [2, n, n] fp32 cross-view target (teacher_blocks.FusedAggregatorBlocks accumulates it while the blocks run)
+                instead of `global_qk` (then None)
     -> dict of targets (None when the NMS leaves no keypoint: the reference then skips the step, :585-588)."""
-    out = None
-    nb = len(global_qk)
-    for i, (q, k) in enumerate(global_qk):
+    if (maps is None) == (global_qk is None):
+        raise GdHipError("extract_vggt_targets: give either global_qk or maps")
+    out = maps
+    nb = len(global_qk or ())
+    for i, (q, k) in enumerate(global_qk or ()):
         out = cross_view_attention_maps(q, k, scale, temperature, prefix, out=out, weight=1.0 / (q.shape[1] * nb), accumulate=i > 0)
     d = depth_map.squeeze(-1) if depth_map.dim() == 4 else depth_map
     Himg, Wimg = d.shape[-2:]

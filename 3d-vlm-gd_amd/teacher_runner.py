@@ -100,37 +100,80 @@ class VGGTTeacherRunner:
     `temperature`; camera_head, depth_head, point_head, track_head).  `pose_decoder(pose_enc, image_hw) -> (extrinsic, intrinsic)`
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
-    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None):
+    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False):
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
         agg = vggt.aggregator
         per = getattr(agg, "aa_block_size", 1)
         # aggregator.forward appends the map of the LAST global block of every selected aa iteration (aggregator.py:255-260)
         self.sel = [agg.global_blocks[i * per + per - 1].attn for i in agg.attn_indices]
+        # fused_blocks: the 2 x depth attention blocks run on the HIP kernels (teacher_blocks.FusedAggregatorBlocks) instead of the user's modules
+        self.fused = None
+        if fused_blocks:
+            from .teacher_blocks import FusedAggregatorBlocks
+            self.fused = FusedAggregatorBlocks(agg, dtype=dtype)
+
+    def _block_inputs(self, rgb_vggt):
+        """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the
+        user's patch embedder, camera / register tokens, position grid) and is left where the blocks begin.  -> tokens [B*S, P, C], pos [B*S, P, 2]."""
+        class _AtBlocks(Exception):
+            pass
+        got = {}
+
+        def stop(mod, args, kwargs):
+            got["tokens"], got["pos"] = args[0], kwargs.get("pos", args[1] if len(args) > 1 else None)
+            raise _AtBlocks
+        h = self.m.aggregator.frame_blocks[0].register_forward_pre_hook(stop, with_kwargs=True)
+        try:
+            self.m.aggregator(rgb_vggt)
+        except _AtBlocks:
+            pass
+        finally:
+            h.remove()
+        if got.get("pos") is None:
+            raise GdHipError("VGGTTeacherRunner: the aggregator gave its first frame block no positions (rope off?): fused_blocks cannot serve it")
+        return got["tokens"], got["pos"]
+
+    @torch.no_grad()
+    def aggregate(self, rgb_vggt):
+        """rgb_vggt [B, S, 3, H, W] -> (tokens_list, ps_idx, qk_or_maps): the aggregator's token outputs and patch start index, and what the
+        cross-view target is built from — the selected global blocks' [(q, k)] off the user's modules (hooks), or, with fused_blocks, the
+        finished maps [2B, n, n]."""
+        agg = self.m.aggregator
+        if self.fused is not None:
+            B, S = rgb_vggt.shape[:2]
+            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda and self.dtype != torch.float32):
+                tokens, pos = self._block_inputs(rgb_vggt)
+            tokens_list, maps = self.fused.forward(tokens, pos, B, S)
+            return tokens_list, agg.patch_start_idx, maps
+        with QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
+            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
+                tokens_list, ps_idx, _ = agg(rgb_vggt)
+        qk = [(q.to(self.dtype) if q.dtype not in (torch.float32, torch.bfloat16) else q,
+               k.to(self.dtype) if k.dtype not in (torch.float32, torch.bfloat16) else k) for q, k in cap.pairs()]
+        return tokens_list, ps_idx, qk
 
     @torch.no_grad()
     def targets(self, rgb_vggt, num_keypoints=300, min_distance=5, generator=None):
         """rgb_vggt [1, 2, 3, H, W] in [0, 1] -> the pair's target dict (teacher_glue.extract_vggt_targets), or None."""
         m, agg = self.m, self.m.aggregator
-        with QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
-            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
-                tokens_list, ps_idx, _ = agg(rgb_vggt)
-            pose_enc = m.camera_head(tokens_list)[-1]
-            dec = self.pose_decoder
-            if dec is None:
-                from vggt.utils.pose_enc import pose_encoding_to_extri_intri as dec       # the user's teacher package
-            extrinsic, intrinsic = dec(pose_enc, rgb_vggt.shape[-2:])
-            depth_map, _ = m.depth_head(tokens_list, rgb_vggt, ps_idx)
-            _, point_conf = m.point_head(tokens_list, rgb_vggt, ps_idx)
+        tokens_list, ps_idx, qk = self.aggregate(rgb_vggt)
+        pose_enc = m.camera_head(tokens_list)[-1]
+        dec = self.pose_decoder
+        if dec is None:
+            from vggt.utils.pose_enc import pose_encoding_to_extri_intri as dec       # the user's teacher package
+        extrinsic, intrinsic = dec(pose_enc, rgb_vggt.shape[-2:])
+        depth_map, _ = m.depth_head(tokens_list, rgb_vggt, ps_idx)
+        _, point_conf = m.point_head(tokens_list, rgb_vggt, ps_idx)
 
         def track(kp1):
             trk, _, _ = m.track_head(tokens_list, rgb_vggt, ps_idx, query_points=kp1[None])
             return trk[-1][0][1]
-        qk = [(q.to(self.dtype) if q.dtype not in (torch.float32, torch.bfloat16) else q,
-               k.to(self.dtype) if k.dtype not in (torch.float32, torch.bfloat16) else k) for q, k in cap.pairs()]
-        scale = float(self.sel[0].scale) if hasattr(self.sel[0], "scale") else qk[0][0].shape[-1] ** -0.5
-        return tg.extract_vggt_targets(qk, depth_map[0], point_conf[0], extrinsic[0], intrinsic[0], track, scale=scale,
+        fused = self.fused is not None
+        scale = float(self.sel[0].scale) if hasattr(self.sel[0], "scale") else (64 if fused else qk[0][0].shape[-1]) ** -0.5
+        return tg.extract_vggt_targets(None if fused else qk, depth_map[0], point_conf[0], extrinsic[0], intrinsic[0], track, scale=scale,
                                        temperature=float(getattr(agg, "temperature", 1.0)), prefix=self.prefix,
-                                       num_keypoints=num_keypoints, min_distance=min_distance, generator=generator)
+                                       num_keypoints=num_keypoints, min_distance=min_distance, generator=generator,
+                                       maps=qk if fused else None)
 
 
 class MASt3RTeacherRunner:

@@ -484,6 +484,15 @@ int gd_post_process_depth(const float* depth, float* out, int P, int H, int W, i
 int gd_rope_2d(void* tokens, const long* positions, int B, int N, int H, int D, long ld_tok, float base, float fwd,
                int dtype, void* stream);
 
+/* The step between the QKV GEMM and the attention product in the VGGT teacher's Attention (vggt/layers/attention.py:58-65: q_norm / k_norm, a
+ * LayerNorm over each head's 64 channels, then rope(q, pos), rope(k, pos)), in place on the packed qkv [B*N, 3*H*64] that gd_attention_fwd
+ * reads (q | k | v, heads inner; f32 | bf16, 16-byte aligned): q <- RoPE2D(LN_64(q; gamma_q, beta_q, eps), pos), k likewise with gamma_k / beta_k;
+ * the v columns are neither read nor written.  gamma / beta: fp32 [64], all four NULL = no normalisation (q_norm = Identity).  The rotation is
+ * gd_rope_2d's (quarters [u_Y, v_Y, u_X, v_X], positions int64 [B*N, 2] as (y, x), forward).  q_out / k_out (both or neither, nullable): the same
+ * results as [B, H, N, 64] in the tensor's dtype — the layout gd_cross_view_attn takes.  No workspace. */
+int gd_qk_norm_rope(void* qkv, const long* positions, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                    void* q_out, void* k_out, int B, int N, int H, int head_dim, float eps, float base, int dtype, void* stream);
+
 /* VGGT teacher -> distillation target: head- (and, through weight / accumulate, block-) averaged cross-view attention maps.
  * Replaces the `return_attn` branch of vggt/layers/attention.py:51-85 (two [B,H,n,n] softmax blocks per global block,
  * torch.cat on dim 0) + the head mean of src/finetune_timm_vggt.py:390-392 + the block mean of vggt/models/aggregator.py:273,

@@ -1,0 +1,158 @@
+"""VGGT teacher block-stack timings on one GPU (not the training benchmark: bench.py stays the yardstick of the step).
+
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24]
+
+1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
+   (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
+   teacher_blocks.FusedAggregatorBlocks) against the same call on the torch modules under bf16 autocast with the q/k hooks (the default
+   path).  Both include the aggregator's own pre-block part (patch embedding, tokens, position grid).  The modules are
+   tests/test_teacher_runner_ref.AggregatorLayout: the aggregator's parameter names and call pattern, not the user's vggt package.
+2. The fused block's kernels one by one at that size (time per call x calls per pair), and gd_qk_norm_rope's bytes per second against
+   its algorithmic bytes — a read and a write of two thirds of qkv — at the pair's size (the tensor fits the Infinity Cache) and on
+   a 64-pair tensor that does not.
+3. "parity": the bf16 pair e_ref / e_hip of tests/test_gpu_teacher_blocks.py (max abs error against the fp64 run of the torch modules under
+   autocast, and of the fused bf16 path), on fixture G22's weights and image.
+Prints one JSON object (also written to --out)."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+import gd_amd  # noqa: E402,F401
+from gd_amd import _lib, ops  # noqa: E402
+from gd_amd.teacher_runner import VGGTTeacherRunner  # noqa: E402
+from bench import PEAK_HBM_GBS, PEAK_TFLOPS  # noqa: E402
+import test_gpu_teacher_blocks as T  # noqa: E402
+from test_teacher_runner_ref import AggregatorLayout  # noqa: E402
+
+HBM_TBS = PEAK_HBM_GBS / 1000.0
+
+
+def timed(fn, warm, iters, reps=1):
+    """ms per call: device events around `reps` back-to-back calls (a kernel of a few microseconds needs several inside one window),
+    `iters` windows after `warm` warm-up calls."""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    singles = []
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        singles.append(e0.elapsed_time(e1) / reps)
+    singles.sort()
+    return {"median_ms": round(singles[len(singles) // 2], 4), "min_ms": round(singles[0], 4), "max_ms": round(singles[-1], 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--warm", type=int, default=2)
+    ap.add_argument("--depth", type=int, default=24)
+    ap.add_argument("--width", type=int, default=1024)
+    ap.add_argument("--img", type=int, default=518)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    res = {"library_sha256_16": hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16], "device": torch.cuda.get_device_name(0)}
+    C, H, S = a.width, a.width // 64, 2
+    P = (a.img // 14) ** 2 + 5
+    with torch.device(dev):
+        agg = AggregatorLayout(img_size=a.img, patch_size=14, embed_dim=C, depth=a.depth, num_heads=H, num_register_tokens=4,
+                               attn_indices=[a.depth // 2, a.depth - 1], temperature=0.8).eval()
+    rope = T.DeviceRope2D()
+    agg.rope = rope
+    for b in list(agg.frame_blocks) + list(agg.global_blocks):
+        b.attn.rope = rope
+        torch.nn.init.constant_(b.ls1.gamma, 0.2)       # a LayerScale that keeps 2 x depth random blocks' residual stream at O(1)
+        torch.nn.init.constant_(b.ls2.gamma, 0.2)
+    teacher = type("Teacher", (), {"aggregator": agg})()
+    img = torch.rand(1, S, 3, a.img, a.img, device=dev)
+    M = S * P
+    flop = 2 * a.depth * (24.0 * M * C * C + 4.0 * M * (P + M) / 2 * C)        # 12 C^2 weights per block; QK^T and PV over N = P (frame) / S P (global)
+    stack = {"width": C, "heads": H, "depth": a.depth, "views": S, "tokens_per_view": P, "flop_per_pair": flop, "dtype": "bf16"}
+    fused = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, fused_blocks=True)
+    hooks = VGGTTeacherRunner(teacher, dtype=torch.bfloat16)
+    # each path twice, interleaved: other work shares the machine
+    stack["fused_aggregate"] = timed(lambda: fused.aggregate(img), a.warm, a.iters)
+    stack["module_aggregate"] = timed(lambda: hooks.aggregate(img), a.warm, a.iters)
+    stack["fused_aggregate_again"] = timed(lambda: fused.aggregate(img), 1, a.iters)
+    stack["module_aggregate_again"] = timed(lambda: hooks.aggregate(img), 1, a.iters)
+    tokens, pos = fused._block_inputs(img)
+    stack["fused_blocks_only"] = timed(lambda: fused.fused.forward(tokens, pos, 1, S), a.warm, a.iters)
+    f_ms = min(stack["fused_aggregate"]["median_ms"], stack["fused_aggregate_again"]["median_ms"])
+    m_ms = min(stack["module_aggregate"]["median_ms"], stack["module_aggregate_again"]["median_ms"])
+    stack["speedup_fused_vs_module"] = round(m_ms / f_ms, 3)
+    stack["fused_blocks_tflops"] = round(flop / stack["fused_blocks_only"]["median_ms"] * 1e-9, 1)
+    stack["fused_blocks_frac_of_bf16_peak"] = round(flop / stack["fused_blocks_only"]["median_ms"] * 1e-9 / PEAK_TFLOPS["bf16"], 4)
+    # agreement of the two paths at this size (random weights, bf16 both): relative to the largest token value
+    tf, _, maps_f = fused.aggregate(img)
+    th, _, qk = hooks.aggregate(img)
+    stack["tokens_rel_diff_fused_vs_module"] = round(max(float((x - y.float()).abs().max() / y.float().abs().max()) for x, y in zip(tf, th)), 5)
+    res["block_stack"] = stack
+
+    # one fused block's kernels at this size
+    p = fused.fused.frame[0]
+    bf = torch.bfloat16
+    x32 = torch.randn(M, C, device=dev)
+    y16 = torch.randn(M, C, device=dev).to(bf)
+    h16 = torch.randn(M, 4 * C, device=dev).to(bf)
+    qkv = torch.randn(M, 3 * C, device=dev).to(bf)
+    posf = pos.to(dev).reshape(M, 2).long().contiguous()
+    per_block = {
+        "layernorm_f32_to_bf16": (2, lambda: ops.layernorm_fwd(x32, p.n1[0], p.n1[1], p.n1[2], save_stats=False, out_dtype=bf)),
+        "gemm_qkv_bias": (1, lambda: ops.gemm_nt(y16, p.wqkv, bias=p.bqkv)),
+        "qk_norm_rope": (1, lambda: ops.qk_norm_rope(qkv, 1, M, H, posf, *p.qk, p.qk_eps, p.base)),
+        "attention_frame": (0.5, lambda: ops.attention_fwd(qkv, S, P, H)),
+        "attention_global": (0.5, lambda: ops.attention_fwd(qkv, 1, M, H)),
+        "gemm_proj_bias_residual_f32": (1, lambda: ops.gemm_nt(y16, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x32)),
+        "gemm_fc1_bias_gelu": (1, lambda: ops.gemm_nt(y16, p.w1, bias=p.b1, act=1)),
+        "gemm_fc2_bias_residual_f32": (1, lambda: ops.gemm_nt(h16, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x32)),
+    }
+    kern, total = {}, 0.0
+    for name, (per, fn) in per_block.items():
+        t = timed(fn, a.warm, a.iters, reps=20)
+        calls = per * 2 * a.depth
+        kern[name] = {"median_ms": t["median_ms"], "calls_per_pair": calls, "ms_per_pair": round(t["median_ms"] * calls, 3)}
+        total += t["median_ms"] * calls
+    kern["sum_ms_per_pair"] = round(total, 3)
+    res["fused_kernels_at_vggt_size"] = kern
+
+    # gd_qk_norm_rope against its algorithmic bytes
+    band = {"hbm_peak_TBs": HBM_TBS}
+    for tag, Bq in (("one_pair", 1), ("64_pairs", 64)):
+        for dt, es in ((bf, 2), (torch.float32, 4)):
+            t_ = torch.randn(Bq * M, 3 * C, device=dev).to(dt)
+            pp = posf.repeat(Bq, 1).contiguous()
+            ms = timed(lambda: ops.qk_norm_rope(t_, Bq, M, H, pp, *p.qk, p.qk_eps, p.base), a.warm, a.iters, reps=20 if Bq == 1 else 3)["median_ms"]
+            nbytes = 2.0 * (2.0 / 3.0) * t_.numel() * es
+            band[f"{tag}_{'bf16' if es == 2 else 'f32'}"] = {"tensor_bytes": t_.numel() * es, "algorithmic_bytes": nbytes, "median_ms": ms,
+                                                             "TBs": round(nbytes / ms * 1e-9, 3), "frac_of_hbm_peak": round(nbytes / ms * 1e-9 / HBM_TBS, 3)}
+            del t_
+    res["qk_norm_rope_bandwidth"] = band
+    del agg, fused, hooks
+    torch.cuda.empty_cache()
+
+    pair = T.bf16_parity_pair()
+    res["parity"] = {k: {"e_ref_torch_autocast": v[0], "e_hip_fused": v[1], "ratio": round(v[1] / v[0], 3)} for k, v in pair.items()}
+    txt = json.dumps(res)
+    print(txt)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
