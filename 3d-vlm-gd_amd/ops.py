@@ -485,6 +485,23 @@ def attention_fwd(qkv, B, N, H, x3=False):
     return o, lse
 
 
+def cross_attention_fwd(q, kv, B, Nq, Nk, H, want_lse=False, x3=False):
+    """q [B*Nq, H*64], kv [B*Nk, 2*H*64] (k | v, heads inner): 2-D tensors or strided 2-D views (last dim contiguous, row strides multiples
+    of 16 bytes) -> o [B*Nq, H*64] contiguous, lse [B,H,Nq] (f32, natural log) or None: softmax(q k^T / 8) v per (image, head)
+    (dust3r/croco/models/blocks.py:150-172).  x3 (fp32 tensors only): the split-precision kernel."""
+    _req(q.is_cuda and kv.is_cuda and q.dtype == kv.dtype, "cross_attention_fwd: q and kv must be CUDA tensors of one dtype")
+    _req(q.dim() == 2 and tuple(q.shape) == (B * Nq, H * 64) and q.stride(1) == 1, "cross_attention_fwd: q must be a [B*Nq, H*64] view, last dim contiguous")
+    _req(kv.dim() == 2 and tuple(kv.shape) == (B * Nk, 2 * H * 64) and kv.stride(1) == 1,
+         "cross_attention_fwd: kv must be a [B*Nk, 2*H*64] view, last dim contiguous")
+    _req(not x3 or q.dtype == torch.float32, "cross_attention_fwd: x3 needs fp32 tensors")
+    o = torch.empty(B * Nq, H * 64, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
+    rc = lib().gd_cross_attention_fwd(ptr(q), ptr(kv), ptr(o), ptr(lse), B, Nq, Nk, H, 64, q.stride(0), kv.stride(0), 64 ** -0.5,
+                                      F32X3 if x3 else dtype_code(q), stream())
+    check(rc, "gd_cross_attention_fwd")
+    return o, lse
+
+
 def attention_bwd(qkv, o, dout, lse, B, N, H, vfirst=False, need_dk=True, x3=False):
     """-> dqkv [B*N, 3*H*64] (same dtype as qkv), column blocks (dq, dk, dv) — or (dq, dv, dk) with vfirst.  need_dk=False: the dK
     columns are left unwritten (bf16: the dK/dV kernel then runs its dV half only)."""

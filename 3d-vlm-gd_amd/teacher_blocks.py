@@ -1,4 +1,7 @@
-"""The VGGT teacher's alternating-attention stack (vggt/models/aggregator.py:246-275: `aa_block_size` frame blocks on [B*S, P], then
+"""The two frozen teachers' transformer stacks on the HIP kernels instead of the user's PyTorch modules: the VGGT aggregator
+(FusedAggregatorBlocks, below) and the MASt3R / CroCo encoder and two-sided decoder (FusedCroCoBlocks, at the end).
+
+The VGGT teacher's alternating-attention stack (vggt/models/aggregator.py:246-275: `aa_block_size` frame blocks on [B*S, P], then
 `aa_block_size` global blocks on [B, S*P], `depth / aa_block_size` times) on the HIP kernels instead of the user's PyTorch modules.
 
 One block (vggt/layers/block.py:81-134 eval path, vggt/layers/attention.py:51-71) runs as
@@ -147,3 +150,194 @@ class FusedAggregatorBlocks:
                     nsel += 1
                 outputs.append(torch.cat([inter[k].view(B, S, P, C), x.view(B, S, P, C)], dim=-1))
         return outputs, maps
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# MASt3R / CroCo: encoder blocks (dust3r/croco/models/blocks.py:115-131) and decoder blocks with cross-attention (blocks.py:133-195)
+# ----------------------------------------------------------------------------------------------------------------------------------
+_WHO = "FusedCroCoBlocks"
+
+
+def _need(obj, attr, name, where):
+    if not hasattr(obj, attr):
+        raise GdHipError(f"{_WHO}: {name}: {where} has no `{attr}`")
+    return getattr(obj, attr)
+
+
+def _affine_ln(m, C, name, nm):
+    if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (C,)):
+        raise GdHipError(f"{_WHO}: {name}: {nm} is not an affine LayerNorm({C})")
+    return m.weight.detach().float().contiguous(), m.bias.detach().float().contiguous(), float(m.eps)
+
+
+def _heads_scale_rope(attn, C, name, what):
+    """-> (H, rope base) of an attention module the kernels serve: head dim 64, scale 64^-0.5, a RoPE module."""
+    H = int(_need(attn, "num_heads", name, what))
+    if C % H or C // H != 64:
+        raise GdHipError(f"{_WHO}: {name}: {what}: head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
+    scale = float(getattr(attn, "scale", 64 ** -0.5))
+    if abs(scale - 64 ** -0.5) > 1e-9:
+        raise GdHipError(f"{_WHO}: {name}: {what}.scale {scale} is not 64^-0.5")
+    rope = getattr(attn, "rope", None)
+    if rope is None:
+        raise GdHipError(f"{_WHO}: {name}: {what}.rope is None: the fused q / k step always rotates")
+    return H, float(getattr(rope, "base_frequency", getattr(rope, "base", 100.0)))
+
+
+class _CroCoBlockParams:
+    """One CroCo block's tensors in the form the kernels take (matrices in the operand dtype, vectors in fp32).  `decoder`: the block also
+    has `cross_attn` (projq / projk / projv / proj), `norm_y` (LayerNorm, or Identity with norm_mem=False) and `norm3`."""
+
+    def __init__(self, blk, name, dtype, decoder):
+        attn, mlp = _need(blk, "attn", name, "the block"), _need(blk, "mlp", name, "the block")
+        C = _need(attn, "qkv", name, "attn").weight.shape[1]
+        self.C = C
+        self.H, self.base = _heads_scale_rope(attn, C, name, "attn")
+        act = getattr(mlp, "act", None)
+        if act is not None and not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
+            raise GdHipError(f"{_WHO}: {name}: mlp.act is {act}: the GEMM epilogue serves exact (erf) GELU")
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+        op = lambda t: t.detach().to(dtype).contiguous()
+        self.n1 = _affine_ln(_need(blk, "norm1", name, "the block"), C, name, "norm1")
+        self.nmlp = _affine_ln(_need(blk, "norm3" if decoder else "norm2", name, "the block"), C, name, "norm3" if decoder else "norm2")
+        self.wqkv, self.bqkv = op(attn.qkv.weight), f32(attn.qkv.bias)
+        proj = _need(attn, "proj", name, "attn")
+        self.wproj, self.bproj = op(proj.weight), f32(proj.bias)
+        self.w1, self.b1 = op(_need(mlp, "fc1", name, "mlp").weight), f32(mlp.fc1.bias)
+        self.w2, self.b2 = op(_need(mlp, "fc2", name, "mlp").weight), f32(mlp.fc2.bias)
+        if not decoder:
+            return
+        ca = _need(blk, "cross_attn", name, "the block")
+        pq, pk, pv, po = (_need(ca, a, name, "cross_attn") for a in ("projq", "projk", "projv", "proj"))
+        Hc, base_c = _heads_scale_rope(ca, C, name, "cross_attn")
+        if (Hc, base_c) != (self.H, self.base):
+            raise GdHipError(f"{_WHO}: {name}: attn and cross_attn differ in heads / RoPE base ({self.H}, {self.base:g} against {Hc}, {base_c:g})")
+        if (pk.bias is None) != (pv.bias is None):
+            raise GdHipError(f"{_WHO}: {name}: cross_attn.projk and projv differ in having a bias")
+        self.n2 = _affine_ln(_need(blk, "norm2", name, "the block"), C, name, "norm2")
+        ny = _need(blk, "norm_y", name, "the block")
+        self.ny = None if isinstance(ny, torch.nn.Identity) else _affine_ln(ny, C, name, "norm_y")
+        self.wq, self.bq = op(pq.weight), f32(pq.bias)
+        # k and v projections of the other view's tokens as ONE GEMM: kv [M, 2C] = [projk | projv], the layout gd_cross_attention_fwd reads
+        self.wkv = op(torch.cat([pk.weight.detach(), pv.weight.detach()], dim=0))
+        self.bkv = None if pk.bias is None else f32(torch.cat([pk.bias.detach(), pv.bias.detach()]))
+        self.wcproj, self.bcproj = op(po.weight), f32(po.bias)
+
+
+class FusedCroCoBlocks:
+    """FusedCroCoBlocks(matcher, dtype=torch.float32): the MASt3R teacher's 24 encoder blocks and 12 + 12 decoder blocks (AsymmetricCroCo3DStereo:
+    `enc_blocks`, `decoder_embed`, `dec_blocks`, `dec_blocks2`, `dec_norm`) on the HIP kernels.  The modules stay the user's: their parameters
+    are read once, here (duck-typed on the attribute names), and anything the kernels do not serve is refused with the block's name.
+
+    dtype: torch.float32 — everything exact fp32, the parity mode and the faithful one (the reference runs this teacher in fp32 with TF32
+    matmuls, dust3r/croco/models/croco.py:12); torch.bfloat16 — bf16 operands, fp32 accumulation, fp32 residual stream: narrower, faster.
+
+    `encode(x, pos)` runs all encoder blocks; `decode(f1, pos1, f2, pos2)` is `_decoder` (dust3r/dust3r/model.py:297-322) with ONE
+    difference in what it returns: the per-layer cross-attention score maps leave as one-head HEAD MEANS [B, 1, Nq, Nk] fp32,
+    (scale / H) * Q K^T over the concatenated heads, taken by one batched GEMM straight off the rotated q and k buffers — never as
+    [B, H, Nq, Nk] per-head tensors.  Both consumers reduce the maps with .mean(dim=1) first (model.py:347-356, both `reciprocity`
+    branches; teacher_glue.mast3r_recip_logits), which leaves a one-head tensor unchanged, so the user's `forward` and the runner's
+    keep_logits path work on them as they are."""
+
+    def __init__(self, matcher, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise GdHipError(f"{_WHO}: dtype must be torch.float32 or torch.bfloat16")
+        for a in ("enc_blocks", "decoder_embed", "dec_blocks", "dec_blocks2", "dec_norm"):
+            if not hasattr(matcher, a):
+                raise GdHipError(f"{_WHO}: the matcher has no `{a}`")
+        if len(matcher.dec_blocks) != len(matcher.dec_blocks2):
+            raise GdHipError(f"{_WHO}: dec_blocks ({len(matcher.dec_blocks)}) and dec_blocks2 ({len(matcher.dec_blocks2)}) differ in length")
+        if len(matcher.dec_blocks) == 0:
+            raise GdHipError(f"{_WHO}: dec_blocks is empty")
+        self.dtype = dtype
+        self.enc = [_CroCoBlockParams(b, f"enc_blocks[{i}]", dtype, False) for i, b in enumerate(matcher.enc_blocks)]
+        self.dec1 = [_CroCoBlockParams(b, f"dec_blocks[{i}]", dtype, True) for i, b in enumerate(matcher.dec_blocks)]
+        self.dec2 = [_CroCoBlockParams(b, f"dec_blocks2[{i}]", dtype, True) for i, b in enumerate(matcher.dec_blocks2)]
+        de = matcher.decoder_embed
+        if not isinstance(de, torch.nn.Linear):
+            raise GdHipError(f"{_WHO}: decoder_embed is {type(de).__name__}, not a Linear")
+        self.wde = de.weight.detach().to(dtype).contiguous()
+        self.bde = None if de.bias is None else de.bias.detach().float().contiguous()
+        Cd = de.weight.shape[0]
+        for p, nm in [(p, f"dec_blocks[{i}]") for i, p in enumerate(self.dec1)] + [(p, f"dec_blocks2[{i}]") for i, p in enumerate(self.dec2)]:
+            if p.C != Cd:
+                raise GdHipError(f"{_WHO}: {nm}: width {p.C} is not decoder_embed's {Cd}")
+        self.dnorm = _affine_ln(matcher.dec_norm, Cd, "dec_norm", "dec_norm")
+
+    # -- pieces ---------------------------------------------------------------------------------------------------------------------
+    def _self_attn(self, p, x, pos, B, N):
+        y, _, _ = ops.layernorm_fwd(x, *p.n1, save_stats=False, out_dtype=self.dtype)
+        qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
+        ops.qk_norm_rope(qkv, B, N, p.H, pos, None, None, None, None, 0.0, p.base)      # null gamma / beta: plain RoPE of q and k
+        o, _ = ops.attention_fwd(qkv, B, N, p.H)
+        return ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x)
+
+    def _mlp(self, p, x):
+        y, _, _ = ops.layernorm_fwd(x, *p.nmlp, save_stats=False, out_dtype=self.dtype)
+        h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
+        return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x)
+
+    def _enc_block(self, p, x, pos, B, N):
+        """x [B*N, C] fp32 residual stream -> the same after one encoder block."""
+        return self._mlp(p, self._self_attn(p, x, pos, B, N))
+
+    def _dec_block(self, p, x, y, xpos, ypos, B, Nx, Ny):
+        """x [B*Nx, C], y [B*Ny, C] fp32 (this view's tokens, the other view's: read only) -> (x after the block, camap [B, 1, Nx, Ny] fp32:
+        the head mean of the raw scaled scores)."""
+        from .rope import rope_2d
+        dt, C, H = self.dtype, p.C, p.H
+        x = self._self_attn(p, x, xpos, B, Nx)
+        xn, _, _ = ops.layernorm_fwd(x, *p.n2, save_stats=False, out_dtype=dt)
+        q = ops.gemm_nt(xn, p.wq, bias=p.bq)
+        if p.ny is not None:
+            yn, _, _ = ops.layernorm_fwd(y, *p.ny, save_stats=False, out_dtype=dt)
+        else:
+            yn = y if dt == torch.float32 else ops.cast(y, dt)                            # norm_mem=False: cast only
+        kv = ops.gemm_nt(yn, p.wkv, bias=p.bkv)
+        rope_2d(q.view(B, Nx, H, 64), xpos.view(B, Nx, 2), p.base, 1.0)                   # in place: ld_tok = C
+        rope_2d(kv.view(B, Ny, 2 * H, 64)[:, :, :H], ypos.view(B, Ny, 2), p.base, 1.0)    # the k half: ld_tok = 2C
+        camap = ops.gemm_nt(q.view(B, Nx, C), kv.view(B, Ny, 2 * C)[:, :, :C], out_dtype=torch.float32, alpha=64 ** -0.5 / H)
+        o, _ = ops.cross_attention_fwd(q, kv, B, Nx, Ny, H)
+        x = ops.gemm_nt(o, p.wcproj, out_dtype=torch.float32, bias=p.bcproj, residual=x)
+        return self._mlp(p, x), camap.unsqueeze(1)
+
+    @staticmethod
+    def _flat(x, pos, C, what):
+        if x.dim() != 3 or x.shape[2] != C or tuple(pos.shape) != (x.shape[0], x.shape[1], 2):
+            raise GdHipError(f"{_WHO}: {what}: tokens {tuple(x.shape)} / pos {tuple(pos.shape)} do not fit width {C}")
+        B, N, _ = x.shape
+        return x.detach().reshape(B * N, C).float().contiguous(), pos.to(x.device).reshape(B * N, 2).long().contiguous(), B, N
+
+    # -- the two entry points ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def encode(self, x, pos):
+        """x [B, N, C] (after the patch embedding), pos [B, N, 2] (y, x) -> [B, N, C] fp32 after all `enc_blocks` (`enc_norm` stays the user's)."""
+        t, p2, B, N = self._flat(x, pos, self.enc[0].C if self.enc else x.shape[-1], "encode")
+        for p in self.enc:
+            t = self._enc_block(p, t, p2, B, N)
+        return t.view(B, N, -1)
+
+    @torch.no_grad()
+    def decode(self, f1, pos1, f2, pos2):
+        """-> (list(zip(*final_output)), camaps1, camaps2), the contract of `_decoder` (model.py:297-322): final_output = [(f1, f2), every
+        layer's pair ...] as fp32 [B, N, C] tensors, the last pair through `dec_norm`; camaps1[l] [B, 1, N1, N2], camaps2[l] [B, 1, N2, N1]:
+        one-head head means (see the class docstring).  Both sides of layer l read the PREVIOUS layer's pair."""
+        Ce = self.wde.shape[1]
+        t1, p1, B, N1 = self._flat(f1, pos1, Ce, "decode view 1")
+        t2, p2, B2, N2 = self._flat(f2, pos2, Ce, "decode view 2")
+        if B2 != B:
+            raise GdHipError(f"{_WHO}: decode: the two views differ in batch size ({B}, {B2})")
+        final = [(t1.view(B, N1, Ce), t2.view(B, N2, Ce))]
+        embed = lambda t: ops.gemm_nt(t if self.dtype == torch.float32 else ops.cast(t, self.dtype), self.wde, out_dtype=torch.float32, bias=self.bde)
+        x1, x2 = embed(t1), embed(t2)
+        camaps1, camaps2 = [], []
+        for pa, pb in zip(self.dec1, self.dec2):
+            n1, c1 = self._dec_block(pa, x1, x2, p1, p2, B, N1, N2)
+            n2, c2 = self._dec_block(pb, x2, x1, p2, p1, B, N2, N1)        # (x1 is still the previous layer's: nothing is updated in place)
+            x1, x2 = n1, n2
+            final.append((x1.view(B, N1, -1), x2.view(B, N2, -1)))
+            camaps1.append(c1)
+            camaps2.append(c2)
+        last = tuple(ops.layernorm_fwd(t, *self.dnorm, save_stats=False, out_dtype=torch.float32)[0] for t in (x1, x2))
+        final[-1] = (last[0].view(B, N1, -1), last[1].view(B, N2, -1))
+        return list(zip(*final)), camaps1, camaps2

@@ -178,11 +178,22 @@ class VGGTTeacherRunner:
 
 class MASt3RTeacherRunner:
     """matcher: the user's AsymmetricMASt3R (the reference's fork returns `tgt_attn_map`, dust3r/dust3r/model.py:346-366);
-    `inference` / `make_pairs`: dust3r.inference.inference and dust3r.image_pairs.make_pairs of the user's package (lazy import)."""
+    `inference` / `make_pairs`: dust3r.inference.inference and dust3r.image_pairs.make_pairs of the user's package (lazy import).
 
-    def __init__(self, matcher, inference=None, make_pairs=None, min_conf_thr=10, subsample=16, keep_logits=False):
+    fused_blocks: the encoder and decoder blocks run on the HIP kernels (teacher_blocks.FusedCroCoBlocks, operand type `dtype`: torch.float32
+    is the faithful mode, the reference runs this teacher in fp32; torch.bfloat16 is narrower and faster).  For the duration of `targets()`
+    only, instance attributes shadow `matcher._decoder` (by FusedCroCoBlocks.decode) and every `enc_blocks[i].forward` (the first runs the whole
+    stack, the others return their input), so the user's own `forward` — patch embedding, `enc_norm`, heads — drives the fused path.  The
+    shadowed `_decoder` returns one-head head-mean score maps [B, 1, Nq, Nk], which `forward`'s and this class's `.mean(dim=1)` leave unchanged."""
+
+    def __init__(self, matcher, inference=None, make_pairs=None, min_conf_thr=10, subsample=16, keep_logits=False, fused_blocks=False,
+                 dtype=torch.float32):
         self.matcher, self.inference, self.make_pairs = matcher, inference, make_pairs
         self.min_conf_thr, self.subsample, self.keep_logits = min_conf_thr, subsample, keep_logits
+        self.fused = None
+        if fused_blocks:
+            from .teacher_blocks import FusedCroCoBlocks
+            self.fused = FusedCroCoBlocks(matcher, dtype=dtype)
 
     @torch.no_grad()
     def targets(self, rgb_mast3r_1, rgb_mast3r_2, temperature=1.0, intrinsic=None, depth_1=None, depth_2=None, device="cuda"):
@@ -195,20 +206,31 @@ class MASt3RTeacherRunner:
         # the decoder's raw cross-attention score maps (dust3r/dust3r/model.py:337, `_decoder` -> dec_feats, tgt_camap, src_camap) are
         # picked up on the way: their head mean / reciprocity average is the temperature-independent part of `tgt_attn_map`, which
         # lets TeacherTargetCache(keep_logits=True) follow the annealed temperature without another teacher forward
-        seen, dec = [], getattr(self.matcher, "_decoder", None)
-        if self.keep_logits and dec is not None:
-            def wrapped(*a, **k):
-                r = dec(*a, **k)
-                if isinstance(r, tuple) and len(r) == 3:
-                    seen.append((r[1], r[2]))
-                return r
-            self.matcher._decoder = wrapped
+        fused = self.fused
+        seen, dec = [], fused.decode if fused is not None else getattr(self.matcher, "_decoder", None)
+        shadowed = []                                   # (object, name) of the instance attributes set here
+
+        def shadow(obj, name, value):
+            setattr(obj, name, value)
+            shadowed.append((obj, name))
         try:
+            if self.keep_logits and dec is not None:
+                def wrapped(*a, **k):
+                    r = dec(*a, **k)
+                    if isinstance(r, tuple) and len(r) == 3:
+                        seen.append((r[1], r[2]))
+                    return r
+                shadow(self.matcher, "_decoder", wrapped)
+            elif fused is not None:
+                shadow(self.matcher, "_decoder", dec)
+            if fused is not None:
+                for i, blk in enumerate(self.matcher.enc_blocks):
+                    shadow(blk, "forward", fused.encode if i == 0 else (lambda x, pos=None: x))
             out = inf(mk([rgb_mast3r_1, rgb_mast3r_2], scene_graph="complete", prefilter=None, symmetrize=True), self.matcher, device,
                       verbose=False)
         finally:
-            if self.keep_logits and dec is not None:
-                del self.matcher._decoder           # the instance attribute shadowing the method
+            for obj, name in reversed(shadowed):
+                delattr(obj, name)                      # the instance attribute shadowing the method: the class's own is visible again
         p1, p2 = out["pred1"], out["pred2"]
         dev = torch.device(device)
         recip = tg.mast3r_recip_logits([t.to(dev) for t in seen[-1][0]], [t.to(dev) for t in seen[-1][1]]) if seen else None

@@ -76,6 +76,14 @@ int gd_attention_fwd(const void* qkv, void* o, float* lse, int B, int N, int H, 
 int gd_attention_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                      int B, int N, int H, int head_dim, float scale, int dtype, int grad_order, void* stream);
 
+/* Multi-head cross-attention forward, head_dim 64, flash-style: the MASt3R teacher's decoder blocks (dust3r/croco/models/blocks.py:150-172,
+ * CrossAttention.forward between the projections and `proj`): o = softmax(q k^T scale) v per (image, head), queries and keys / values from
+ * different token sets of different length.  q [B,Nq,H*64] with row stride ldq elements (>= H*64; image stride Nq*ldq); kv [B,Nk,2,H,64]
+ * (k | v, heads inner) with row stride ldkv elements (>= 2*H*64; image stride Nk*ldkv); o [B,Nq,H*64] contiguous; lse [B,H,Nq] f32 (natural
+ * log), nullable.  Strides are multiples of 16 bytes, pointers 16-byte aligned; dtype GD_F32 | GD_BF16 | GD_F16 | GD_F32X3. */
+int gd_cross_attention_fwd(const void* q, const void* kv, void* o, float* lse, int B, int Nq, int Nk, int H, int head_dim,
+                           long ldq, long ldkv, float scale, int dtype, void* stream);
+
 /* LoRA backward of one block in one pass (utils/model.py:57-71): dt [M,8] f32 = dqv [M,K] . bt^T and gbt [8,K] f32 += t^T . dqv for
  * the bf16 (dq, dv) gradient block dqv (row stride ldx elements), t [M,8] f32 the saved rank projections, bt [8,K] bf16 the B factors
  * transposed.  bt == NULL: only the second product (dt may be NULL too) — any [8, K] += t^T . X with an [M, 8] f32 left operand, e.g. the

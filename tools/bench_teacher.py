@@ -1,6 +1,6 @@
-"""VGGT teacher block-stack timings on one GPU (not the training benchmark: bench.py stays the yardstick of the step).
+"""Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -12,7 +12,13 @@
    a 64-pair tensor that does not.
 3. "parity": the bf16 pair e_ref / e_hip of tests/test_gpu_teacher_blocks.py (max abs error against the fp64 run of the torch modules under
    autocast, and of the fused bf16 path), on fixture G22's weights and image.
-Prints one JSON object (also written to --out)."""
+4. "mast3r_block_stack": the MASt3R teacher's transformer at its size — ViT-L encoder 24 x 1024 / 16 heads, decoder 12 + 12 x 768 / 12 heads, two views
+   of 768 tokens (24 x 32), B = 2 (the symmetrised pair), random weights: encoder blocks, `enc_norm`, decoder and target map through
+   teacher_blocks.FusedCroCoBlocks (f32 and bf16) against the torch modules of tests/croco_layout.py (f32, and under bf16 autocast) in the same
+   process, alternating.  "cross_attention_kernel": gd_cross_attention_fwd alone at (B, Nq, Nk, H) = (2, 768, 768, 12) per element type, from device
+   events around 20 back-to-back calls, with the achieved TFLOP/s of its 4 B H Nq Nk 64 operations.  "parity" / "mast3r": the measured values of
+   tests/test_gpu_mast3r_blocks.py (f32 stack against fixture G25 with the measured bound of the target map; the bf16 pair e_ref / e_hip).
+Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
 import json
@@ -29,6 +35,8 @@ import gd_amd  # noqa: E402,F401
 from gd_amd import _lib, ops  # noqa: E402
 from gd_amd.teacher_runner import VGGTTeacherRunner  # noqa: E402
 from bench import PEAK_HBM_GBS, PEAK_TFLOPS  # noqa: E402
+import croco_layout as CL  # noqa: E402
+import test_gpu_mast3r_blocks as TM  # noqa: E402
 import test_gpu_teacher_blocks as T  # noqa: E402
 from test_teacher_runner_ref import AggregatorLayout  # noqa: E402
 
@@ -62,10 +70,100 @@ def main():
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--img", type=int, default=518)
+    ap.add_argument("--sections", default="vggt,mast3r")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    res = {"library_sha256_16": hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16], "device": torch.cuda.get_device_name(0)}
+    res = {}
+    if a.out and os.path.exists(a.out):
+        res = json.load(open(a.out))
+    res.update({"library_sha256_16": hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16], "device": torch.cuda.get_device_name(0)})
+    sections = a.sections.split(",")
+    if "vggt" in sections:
+        vggt_sections(res, a, dev)
+    if "mast3r" in sections:
+        mast3r_sections(res, a, dev)
+    txt = json.dumps(res)
+    print(txt)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def mast3r_sections(res, a, dev):
+    from gd_amd import teacher_glue as tg
+    from gd_amd.teacher_blocks import FusedCroCoBlocks
+    B, grid = 2, (24, 32)
+    N = grid[0] * grid[1]
+    cfg = dict(enc_dim=1024, enc_heads=16, enc_depth=a.depth, dec_dim=768, dec_heads=12, dec_depth=a.depth // 2, temperature=3.0, reciprocity=True)
+    with torch.device(dev):
+        m = CL.CrocoLayout(**cfg).eval()
+    x1, x2 = torch.randn(B, N, cfg["enc_dim"], device=dev), torch.randn(B, N, cfg["enc_dim"], device=dev)
+    pos = CL.grid_positions(B, *grid).to(dev)
+    Ce, Cd, Le, Ld = cfg["enc_dim"], cfg["dec_dim"], cfg["enc_depth"], cfg["dec_depth"]
+    M = 2 * B * N                                            # token rows of both views
+    # encoder: 12 C^2 weights per block + QK^T and PV; decoder block: 4 C^2 (self) + 4 C^2 (cross: q, k, v, proj) + 8 C^2 (MLP) + two attention products
+    # + the head-mean score GEMM; decoder_embed
+    flop = (Le * (24.0 * M * Ce * Ce + 4.0 * M * N * Ce) + 2.0 * M * Ce * Cd + Ld * (32.0 * M * Cd * Cd + 8.0 * M * N * Cd + 2.0 * M * N * Cd))
+    stack = dict(cfg, B=B, tokens_per_view=N, flop_per_pair=flop)
+
+    def fused_run(f):
+        e1, e2 = f.encode(x1, pos), f.encode(x2, pos)
+        outs, c1, c2 = f.decode(m.enc_norm(e1), pos, m.enc_norm(e2), pos)
+        return outs, tg.mast3r_tgt_attn_map(c1, c2, m.temperature)
+
+    def module_run(autocast):
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            e1, e2 = m.encode_blocks(x1, pos), m.encode_blocks(x2, pos)
+            return m.target(m.enc_norm(e1), pos, m.enc_norm(e2), pos)
+    f32, bf = FusedCroCoBlocks(m, dtype=torch.float32), FusedCroCoBlocks(m, dtype=torch.bfloat16)
+    paths = {"fused_f32": lambda: fused_run(f32), "module_f32": lambda: module_run(False), "fused_bf16": lambda: fused_run(bf),
+             "module_bf16_autocast": lambda: module_run(True)}
+    # each path twice, interleaved: other work shares the machine
+    for name, fn in paths.items():
+        stack[name] = timed(fn, a.warm, a.iters)
+    for name, fn in paths.items():
+        stack[name + "_again"] = timed(fn, 1, a.iters)
+    best = lambda k: min(stack[k]["median_ms"], stack[k + "_again"]["median_ms"])
+    stack["speedup_fused_f32_vs_module_f32"] = round(best("module_f32") / best("fused_f32"), 3)
+    stack["speedup_fused_bf16_vs_module_bf16_autocast"] = round(best("module_bf16_autocast") / best("fused_bf16"), 3)
+    stack["fused_f32_tflops"] = round(flop / best("fused_f32") * 1e-9, 1)
+    stack["fused_bf16_tflops"] = round(flop / best("fused_bf16") * 1e-9, 1)
+    # agreement of the paths at this size (random weights): last decoder output relative to its largest value, and the target map
+    (of, tf_), (om, tm) = fused_run(f32), module_run(False)
+    stack["f32_last_output_rel_diff_fused_vs_module"] = float((of[0][-1] - om[0][-1]).abs().max() / om[0][-1].abs().max())
+    stack["f32_tgt_attn_map_max_abs_diff_fused_vs_module"] = float((tf_ - tm).abs().max())
+    (ob, tb), (oa, ta) = fused_run(bf), module_run(True)
+    stack["bf16_last_output_rel_diff_vs_module_f32"] = {"fused": float((ob[0][-1] - om[0][-1]).abs().max() / om[0][-1].abs().max()),
+                                                        "module_autocast": float((oa[0][-1].float() - om[0][-1]).abs().max() / om[0][-1].abs().max())}
+    res["mast3r_block_stack"] = stack
+    del f32, bf, m
+    torch.cuda.empty_cache()
+
+    H = 12
+    kflop = 4.0 * B * H * N * N * 64
+    kern = {"shape_B_Nq_Nk_H": [B, N, N, H], "flop": kflop}
+    for name, dt, x3, peak in (("f32", torch.float32, False, "f32"), ("bf16", torch.bfloat16, False, "bf16"), ("f16", torch.float16, False, "bf16"),
+                               ("f32x3", torch.float32, True, "bf16")):
+        q, kv = torch.randn(B * N, H * 64, device=dev).to(dt), torch.randn(B * N, 2 * H * 64, device=dev).to(dt)
+        t = timed(lambda: ops.cross_attention_fwd(q, kv, B, N, N, H, x3=x3), a.warm, max(a.iters, 5), reps=20)
+        kern[name] = dict(t, tflops=round(kflop / t["median_ms"] * 1e-9, 1))
+        if peak in PEAK_TFLOPS and name != "f32x3":
+            kern[name]["frac_of_peak"] = round(kflop / t["median_ms"] * 1e-9 / PEAK_TFLOPS[peak], 4)
+    res["cross_attention_kernel"] = kern
+
+    g, enc, outs, c1, c2, tgt, e32 = TM.f32_parity()
+    named = [("enc_1", enc[0]), ("enc_2", enc[1])] + [(f"out{v + 1}_{i}", t) for v in range(2) for i, t in enumerate(outs[v])]
+    named += [(f"camap1_{l}", t) for l, t in enumerate(c1)] + [(f"camap2_{l}", t) for l, t in enumerate(c2)]
+    par = {"f32_vs_g25_worst_e_over_max": max(TM.max_abs(t, g[n]) / float(g[n].abs().max()) for n, t in named), "f32_tokens_bound_e_over_max": 1e-4,
+           "f32_tgt_attn_map_e": TM.max_abs(tgt, g["tgt_attn_map"]), "e32_layout_f32_vs_f64": e32, "f32_tgt_attn_map_bound": max(TM.TGT_TOL, 4 * e32)}
+    for k, v in TM.bf16_parity_pair().items():
+        par["bf16_" + k] = {"e_ref_torch_autocast": v[0], "e_hip_fused": v[1], "ratio": round(v[1] / v[0], 3)}
+    res.setdefault("parity", {})["mast3r"] = par
+
+
+def vggt_sections(res, a, dev):
     C, H, S = a.width, a.width // 64, 2
     P = (a.img // 14) ** 2 + 5
     with torch.device(dev):
@@ -145,13 +243,7 @@ def main():
     torch.cuda.empty_cache()
 
     pair = T.bf16_parity_pair()
-    res["parity"] = {k: {"e_ref_torch_autocast": v[0], "e_hip_fused": v[1], "ratio": round(v[1] / v[0], 3)} for k, v in pair.items()}
-    txt = json.dumps(res)
-    print(txt)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
+    res.setdefault("parity", {}).update({k: {"e_ref_torch_autocast": v[0], "e_hip_fused": v[1], "ratio": round(v[1] / v[0], 3)} for k, v in pair.items()})
 
 
 if __name__ == "__main__":
