@@ -99,6 +99,10 @@ SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_stack3_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p]),
     "gd_unpitch_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gd_grid_resample": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_void_p]),
+    "gd_deconv_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gd_dpt_head_out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_tap_mean_fwd": (c_int, [ctypes.POINTER(c_void_p), c_int, c_long, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                 c_void_p]),
     "gd_tap_mean_norm_fwd": (c_int, [ctypes.POINTER(c_void_p), c_int, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -892,6 +892,50 @@ def unpitch_tokens(src, B, gh, gw, D, prefix):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ DPT head glue (csrc/dpt.hip)
+DPT_ACT = {"linear": 0, "exp": 1, "inv_log": 2, "relu": 3, "sigmoid": 4}            # include/gd_hip.h GD_DPT_ACT_*
+DPT_CONF_ACT = {"expp1": 0, "expp0": 1, "sigmoid": 2, "linear": 3}                  # GD_DPT_CONF_* ("linear": the pre-activation map)
+
+
+def grid_resample(src, frames, sh, sw, dh, dw, C, *, step=0, addend=None, px=None, py=None, relu=False, stacked=None):
+    """src: the pitched grid [frames*sh*(sw+1), C] (f32 | bf16) -> dh x dw (gd_grid_resample: bilinear align_corners=True, or every `step`-th
+    pixel), + addend [frames*dh*(dw+1), C] + position tables px [dw, C/2], py [dh, C/2] (fp32), ReLU last.
+    stacked=None: the pitched fp32 grid [frames*dh*(dw+1), C], separators zero;  stacked=dtype: the stack3_rows operand of that grid,
+    [frames*dh*(dw+1) + 2, 3C] of `dtype`, written directly."""
+    _req(src.is_cuda and src.is_contiguous() and src.numel() == frames * sh * (sw + 1) * C, "grid_resample: src is not the contiguous pitched grid")
+    for t, n, what in ((addend, frames * dh * (dw + 1) * C, "addend"), (px, dw * (C // 2), "px"), (py, dh * (C // 2), "py")):
+        _req(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n), f"grid_resample: bad {what}")
+    rows = frames * dh * (dw + 1)
+    out = torch.empty((rows, C) if stacked is None else (rows + 2, 3 * C), dtype=stacked or torch.float32, device=src.device)
+    check(lib().gd_grid_resample(ptr(src), dtype_code(src), ptr(out), dtype_code(out), 0 if stacked is None else 1, frames, sh, sw, dh, dw, C, int(step),
+                                 ptr(addend), ptr(px), ptr(py), 1 if relu else 0, stream()), "gd_grid_resample")
+    return out
+
+
+def deconv_scatter(src, bias, frames, gh, gw, src_pitch, k, Cout):
+    """src [frames*gh*src_pitch, k*k*Cout] fp32 (the transposed convolution's GEMM output, columns (ky, kx, n)) -> the pitched grid
+    [frames*gh*k*(gw*k+1), Cout] + bias."""
+    _req(src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and tuple(src.shape) == (frames * gh * src_pitch, k * k * Cout) and
+         bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout, "deconv_scatter: bad src / bias")
+    out = torch.empty(frames * gh * k * (gw * k + 1), Cout, dtype=torch.float32, device=src.device)
+    check(lib().gd_deconv_scatter(ptr(src), ptr(bias), ptr(out), frames, gh, gw, src_pitch, k, Cout, stream()), "gd_deconv_scatter")
+    return out
+
+
+def dpt_head_out(x, w, bias, frames, H, W, activation, conf_activation):
+    """x: pitched [frames*H*(W+1), Cin] fp32, w [od, Cin], bias [od] -> preds [frames, H, W, od-1], conf [frames, H, W] (gd_dpt_head_out)."""
+    _req(activation in DPT_ACT, f"dpt_head_out: activation {activation!r}: served are {sorted(DPT_ACT)}")
+    _req(conf_activation in DPT_CONF_ACT, f"dpt_head_out: conf_activation {conf_activation!r}: served are {sorted(DPT_CONF_ACT)}")
+    od, Cin = w.shape
+    _req(all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (x, w, bias)) and tuple(x.shape) == (frames * H * (W + 1), Cin) and
+         bias.numel() == od, "dpt_head_out: bad x / w / bias")
+    preds = torch.empty(frames, H, W, max(od - 1, 0), dtype=torch.float32, device=x.device)
+    conf = torch.empty(frames, H, W, dtype=torch.float32, device=x.device)
+    check(lib().gd_dpt_head_out(ptr(x), ptr(w), ptr(bias), ptr(preds), ptr(conf), frames, H, W, Cin, od, DPT_ACT[activation],
+                                DPT_CONF_ACT[conf_activation], stream()), "gd_dpt_head_out")
+    return preds, conf
+
+
 class _TapMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prefix, with_norm, *grids):

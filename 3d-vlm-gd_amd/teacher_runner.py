@@ -10,7 +10,8 @@ PyTorch-ROCm inference).  What lives here is the glue around them:
   `return_attn` branch materialises (`vggt/layers/attention.py:73-84`: 480 MB per pair and block at n = 1369);
 * `VGGTTeacherRunner` — `extract_vggt_features` + `sample_keypoints` (src/finetune_timm_vggt.py:357-449) as one call that returns the
   pair's targets in the cache layout; the reference aggregator's hard-wired `return_attn=True` is neutralised for the duration of the
-  call (the selected blocks return a 1-element placeholder instead of the maps);
+  call (the selected blocks return a 1-element placeholder instead of the maps); with `fused_heads` the three dense-prediction heads run on
+  the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules;
 * `MASt3RTeacherRunner` — `extract_mast3r_features` + `filter_and_match_keypoints` + the depth branch
   (src/finetune_timm_mast3r.py:345-469, 617-633) around the user's `dust3r.inference.inference`.
 """
@@ -100,7 +101,7 @@ class VGGTTeacherRunner:
     `temperature`; camera_head, depth_head, point_head, track_head).  `pose_decoder(pose_enc, image_hw) -> (extrinsic, intrinsic)`
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
-    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False):
+    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32):
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
         agg = vggt.aggregator
         per = getattr(agg, "aa_block_size", 1)
@@ -111,6 +112,13 @@ class VGGTTeacherRunner:
         if fused_blocks:
             from .teacher_blocks import FusedAggregatorBlocks
             self.fused = FusedAggregatorBlocks(agg, dtype=dtype)
+        # fused_heads: the three dense-prediction heads run on the HIP kernels (teacher_heads.FusedDPTHead, operand type `heads_dtype`: torch.float32 is
+        # the faithful mode, the reference runs its heads in fp32).  Independent of fused_blocks; a head the class refuses raises here, not in targets().
+        self.heads = None
+        if fused_heads:
+            from .teacher_heads import FusedDPTHead
+            self.heads = {n: FusedDPTHead(h, dtype=heads_dtype, name=n) for n, h in (("depth_head", vggt.depth_head), ("point_head", vggt.point_head),
+                                                                                      ("track_head.feature_extractor", vggt.track_head.feature_extractor))}
 
     def _block_inputs(self, rgb_vggt):
         """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the
@@ -162,11 +170,20 @@ class VGGTTeacherRunner:
         if dec is None:
             from vggt.utils.pose_enc import pose_encoding_to_extri_intri as dec       # the user's teacher package
         extrinsic, intrinsic = dec(pose_enc, rgb_vggt.shape[-2:])
-        depth_map, _ = m.depth_head(tokens_list, rgb_vggt, ps_idx)
-        _, point_conf = m.point_head(tokens_list, rgb_vggt, ps_idx)
+        heads = self.heads
+        depth_map, _ = (heads["depth_head"] if heads else m.depth_head)(tokens_list, rgb_vggt, ps_idx)
+        _, point_conf = (heads["point_head"] if heads else m.point_head)(tokens_list, rgb_vggt, ps_idx)
 
         def track(kp1):
-            trk, _, _ = m.track_head(tokens_list, rgb_vggt, ps_idx, query_points=kp1[None])
+            # with fused heads, for this call only, an instance attribute shadows the feature extractor's forward: the user's track_head drives the fused head
+            fe = m.track_head.feature_extractor if heads else None
+            if fe is not None:
+                fe.forward = heads["track_head.feature_extractor"].forward
+            try:
+                trk, _, _ = m.track_head(tokens_list, rgb_vggt, ps_idx, query_points=kp1[None])
+            finally:
+                if fe is not None:
+                    del fe.forward          # the class's own forward is visible again
             return trk[-1][0][1]
         fused = self.fused is not None
         scale = float(self.sel[0].scale) if hasattr(self.sel[0], "scale") else (64 if fused else qk[0][0].shape[-1]) ** -0.5

@@ -170,6 +170,34 @@ int gd_stack3_rows(const void* src, void* dst, int B, int gh, int gw, int D, lon
 int gd_unpitch_tokens(const void* src, void* dst, int B, int gh, int gw, int D, int prefix, int dtype, void* stream);
 int gd_im2col3x3(const void* x, long bstride, void* col, int B, int gh, int gw, int D, int dtype, void* stream);
 int gd_col2im3x3(const void* dcol, void* dx, long bstride, int B, int gh, int gw, int D, int dtype, void* stream);
+/* The spatial glue of a DPT dense-prediction head (vggt/heads/dpt_head.py) on the same layout: every grid is channel-last with one separator
+ * column, [frames, gh * (gw + 1), C], C a multiple of 8.
+ * gd_grid_resample: source grid sh x sw (f32 | bf16) -> dh x dw.  step = 0: bilinear, align_corners=True (source coordinate dst * (s - 1) / (d - 1),
+ * 0 when d = 1; equal sizes are a bit-exact copy); step >= 1: source pixel (y * step, x * step) (a stride-`step` subsample; step = 1 with equal sizes
+ * is the copy).  Then + addend [frames, dh * (dw + 1), C] (f32, or null), + the separable position tables px [dw, C/2], py [dh, C/2] (f32, or both
+ * null): out[y, x, :C/2] += px[x], out[y, x, C/2:] += py[y]; then ReLU when `relu`.  stacked = 0: dst is the pitched f32 grid, separators written as
+ * zero; stacked = 1: dst (f32 | bf16) is what gd_stack3_rows would write from that grid, [frames * dh * (dw + 1) + 2, 3 C] — the resampled map is
+ * never stored on its own. */
+int gd_grid_resample(const void* src, int src_dtype, void* dst, int dst_dtype, int stacked, int frames, int sh, int sw, int dh, int dw, int C, int step,
+                     const float* addend, const float* px, const float* py, int relu, void* stream);
+/* ConvTranspose2d with kernel = stride = k after its GEMM: src [frames * gh * src_pitch, k * k * C_out] = rows x [(ky, kx, n), C_in]^T (f32; src_pitch
+ * = gw for token rows, gw + 1 for a pitched grid whose separator rows are dropped) -> dst the pitched grid (gh k) x (gw k) of C_out channels,
+ * + bias [C_out], separators zero.  C_out a multiple of 4, k <= 8. */
+int gd_deconv_scatter(const float* src, const float* bias, float* dst, int frames, int gh, int gw, int src_pitch, int k, int Cout, void* stream);
+/* The head's last layer (1x1 convolution C_in -> output_dim, split, vggt/heads/head_act.py activate_head): x the pitched map [frames * H * (W + 1),
+ * C_in] (f32, already rectified), w [output_dim, C_in], bias [output_dim] -> preds [frames, H, W, output_dim - 1] = act(first channels),
+ * conf [frames, H, W] = conf_act(last channel), f32, no separators.  2 <= output_dim <= 8, C_in a multiple of 4. */
+#define GD_DPT_ACT_LINEAR 0
+#define GD_DPT_ACT_EXP 1
+#define GD_DPT_ACT_INV_LOG 2     /* sign(y) expm1(|y|) */
+#define GD_DPT_ACT_RELU 3
+#define GD_DPT_ACT_SIGMOID 4
+#define GD_DPT_CONF_EXPP1 0      /* 1 + exp(y) */
+#define GD_DPT_CONF_EXPP0 1      /* exp(y) */
+#define GD_DPT_CONF_SIGMOID 2
+#define GD_DPT_CONF_LINEAR 3     /* y itself: the pre-activation map */
+int gd_dpt_head_out(const float* x, const float* w, const float* bias, float* preds, float* conf, int frames, int H, int W, int Cin, int output_dim,
+                    int act, int conf_act, void* stream);
 /* interpolate_features (utils/functions.py:55-76) on 1..4 token-major grids, averaged; backward scatters into fp32
  * gradient grids (batch stride bstride elements, pre-zeroed).  pitch = tokens per grid line in memory (gw for a dense grid,
  * gw + 1 for the separator-column layout of gd_stack3_rows' GEMM output). */

@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -18,6 +18,13 @@
    process, alternating.  "cross_attention_kernel": gd_cross_attention_fwd alone at (B, Nq, Nk, H) = (2, 768, 768, 12) per element type, from device
    events around 20 back-to-back calls, with the achieved TFLOP/s of its 4 B H Nq Nk 64 operations.  "parity" / "mast3r": the measured values of
    tests/test_gpu_mast3r_blocks.py (f32 stack against fixture G25 with the measured bound of the target map; the bf16 pair e_ref / e_hip).
+5. "vggt_dpt_heads" (--sections heads): ONE dense-prediction head at VGGT-1B size — dim_in 2048, 256 features, out_channels [256, 512, 1024, 1024], two
+   frames of 518^2, random weights: teacher_heads.FusedDPTHead (f32 and bf16 operands) against the torch module of tests/dpt_layout.py (f32, and
+   under bf16 autocast) in the same process, alternating; the fused path's GEMM FLOP (counted by ops.GemmProfiler), its peak workspace (the
+   allocator's peak above what was resident before the call) and the agreement of the f32 paths on the map before the activations.
+   "vggt_dpt_heads_share_of_targets" (--sections heads_share): a VGGT-shaped random-weight teacher (the aggregator at --depth / --width with fused_blocks, depth and
+   point heads, a track head whose feature extractor is a 128-feature head at down_ratio 2 around a stub tracker): the three heads' time, on the
+   modules and fused, beside `aggregate` and the whole `targets()` call.
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -77,18 +84,120 @@ def main():
     res = {}
     if a.out and os.path.exists(a.out):
         res = json.load(open(a.out))
-    res.update({"library_sha256_16": hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16], "device": torch.cuda.get_device_name(0)})
+    res.pop("library_sha256_16", None)          # (files of earlier runs: one hash for the whole file; it is kept per section now)
+    res["device"] = torch.cuda.get_device_name(0)
     sections = a.sections.split(",")
     if "vggt" in sections:
         vggt_sections(res, a, dev)
     if "mast3r" in sections:
         mast3r_sections(res, a, dev)
+    if "heads" in sections:
+        dpt_head_section(res, a, dev)
+    if "heads_share" in sections:
+        dpt_share_section(res, a, dev)
+    # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
+    lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
+    ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
+           "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"]}
+    for sec in sections:
+        for key in ran.get(sec, []):
+            if key in res:
+                res[key]["library_sha256_16"] = lib_hash
     txt = json.dumps(res)
     print(txt)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
+
+
+VGGT_HEAD = dict(dim_in=2048, features=256, out_channels=[256, 512, 1024, 1024])
+
+
+def dpt_head_section(res, a, dev):
+    import dpt_layout as DL
+    from gd_amd.teacher_heads import FusedDPTHead
+    S, P = 2, (a.img // 14) ** 2 + 5
+    with torch.device(dev):
+        m = DL.DPTLayout(output_dim=2, activation="exp", conf_activation="expp1", **VGGT_HEAD).eval()
+    toks = [torch.randn(1, S, P, VGGT_HEAD["dim_in"], device=dev) for _ in range(4)]
+    img = torch.rand(1, S, 3, (a.img // 14) * 14, (a.img // 14) * 14, device=dev)
+    f32, bf = FusedDPTHead(m, dtype=torch.float32), FusedDPTHead(m, dtype=torch.bfloat16)
+
+    def module_run(autocast, taps=None):
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            return m(toks, img, 5, taps=taps)
+    paths = {"fused_f32": lambda: f32.forward(toks, img, 5), "module_f32": lambda: module_run(False), "fused_bf16": lambda: bf.forward(toks, img, 5),
+             "module_bf16_autocast": lambda: module_run(True)}
+    out = dict(VGGT_HEAD, frames=S, image=list(img.shape[-2:]), patch_grid=[a.img // 14, a.img // 14])
+    prof = ops.GemmProfiler()
+    ops.set_gemm_profiler(prof)
+    f32.forward(toks, img, 5)
+    ops.set_gemm_profiler(None)
+    flop, _, launches = prof.totals()
+    out["fused_gemm_flop"], out["fused_gemm_launches"] = flop, launches
+    for name in ("fused_f32", "fused_bf16", "module_f32", "module_bf16_autocast"):
+        paths[name]()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        paths[name]()
+        torch.cuda.synchronize()
+        out[name + "_peak_workspace_MB"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+    # each path twice, interleaved: other work shares the machine
+    for name, fn in paths.items():
+        out[name] = timed(fn, a.warm, a.iters)
+    for name, fn in paths.items():
+        out[name + "_again"] = timed(fn, 1, a.iters)
+    best = lambda k: min(out[k]["median_ms"], out[k + "_again"]["median_ms"])
+    out["speedup_fused_f32_vs_module_f32"] = round(best("module_f32") / best("fused_f32"), 3)
+    out["speedup_fused_bf16_vs_module_bf16_autocast"] = round(best("module_bf16_autocast") / best("fused_bf16"), 3)
+    out["fused_f32_tflops"] = round(flop / best("fused_f32") * 1e-9, 1)
+    out["fused_bf16_tflops"] = round(flop / best("fused_bf16") * 1e-9, 1)
+    tf, tm, tb, ta = {}, {}, {}, {}
+    f32.forward(toks, img, 5, taps=tf), module_run(False, tm), bf.forward(toks, img, 5, taps=tb), module_run(True, ta)
+    rel = lambda x, y: float((x.float() - y).abs().max() / y.abs().max())
+    out["pre_activation_rel_diff_vs_module_f32"] = {"fused_f32": rel(tf["pre"], tm["pre"]), "fused_bf16": rel(tb["pre"], tm["pre"]),
+                                                    "module_bf16_autocast": rel(ta["pre"], tm["pre"])}
+    res["vggt_dpt_heads"] = out
+
+
+def dpt_share_section(res, a, dev):
+    import dpt_layout as DL
+    C, S = a.width, 2
+    idx = [a.depth // 6, a.depth // 2 - 1, 3 * a.depth // 4 - 1, a.depth - 1]          # [4, 11, 17, 23] at depth 24
+    with torch.device(dev):
+        agg = AggregatorLayout(img_size=a.img, patch_size=14, embed_dim=C, depth=a.depth, num_heads=C // 64, num_register_tokens=4,
+                               attn_indices=[a.depth // 2, a.depth - 1], temperature=0.8).eval()
+        head = lambda **kw: DL.DPTLayout(**dict(dict(VGGT_HEAD, dim_in=2 * C), intermediate_layer_idx=idx, **kw)).eval()
+        track = DL.TinyTrackHead(2 * C)
+        track.feature_extractor = head(features=128, feature_only=True, down_ratio=2)
+        depth_head, point_head = head(output_dim=2, activation="exp"), head(output_dim=4, activation="inv_log")
+    rope = T.DeviceRope2D()
+    agg.rope = rope
+    for b in list(agg.frame_blocks) + list(agg.global_blocks):
+        b.attn.rope = rope
+        torch.nn.init.constant_(b.ls1.gamma, 0.2)
+        torch.nn.init.constant_(b.ls2.gamma, 0.2)
+    teacher = type("Teacher", (), {"aggregator": agg, "depth_head": depth_head, "point_head": point_head,
+                                   "track_head": track.eval(), "camera_head": lambda self, toks: [torch.zeros(1, 2, 9, device=dev)]})()
+    img = torch.rand(1, S, 3, (a.img // 14) * 14, (a.img // 14) * 14, device=dev)
+    out = {"width": C, "depth": a.depth, "intermediate_layer_idx": idx, "aggregator": "fused_blocks bf16", "track_feature_extractor": "128 features, down_ratio 2"}
+    for tag, fused_heads in (("module_heads_f32", False), ("fused_heads_f32", True)):
+        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=fused_heads)
+        toks, ps, _ = r.aggregate(img)
+        hs = r.heads or {"depth_head": teacher.depth_head, "point_head": teacher.point_head, "track_head.feature_extractor": track.feature_extractor}
+
+        def heads_run():
+            with torch.no_grad():
+                for h in hs.values():
+                    h(toks, img, ps)
+        got = r.targets(img)
+        out[tag] = {"aggregate": timed(lambda: r.aggregate(img), 1, a.iters), "three_heads": timed(heads_run, a.warm, a.iters),
+                    "targets": timed(lambda: r.targets(img), 1, a.iters), "targets_returned_none": got is None}
+        out[tag]["heads_share_of_targets"] = round(out[tag]["three_heads"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
+        del r
+    res["vggt_dpt_heads_share_of_targets"] = out
 
 
 def mast3r_sections(res, a, dev):
