@@ -103,6 +103,7 @@ SIGNATURES = {
                                  c_int, c_void_p]),
     "gd_deconv_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_dpt_head_out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gd_mast3r_head_out": (c_int, [c_void_p] * 8 + [c_int] * 10 + [c_float, c_float, c_int, c_int, c_float, c_float, c_void_p]),
     "gd_tap_mean_fwd": (c_int, [ctypes.POINTER(c_void_p), c_int, c_long, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                 c_void_p]),
     "gd_tap_mean_norm_fwd": (c_int, [ctypes.POINTER(c_void_p), c_int, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -1,6 +1,7 @@
-// The spatial glue of a DPT dense-prediction head (vggt/heads/dpt_head.py) around gd_gemm_nt: every grid is channel-last on the separator-column
-// layout of gd_stack3_rows, [frames, gh * (gw + 1), C], so that each 3x3 convolution of the head is one GEMM on the overlapping-row view of a
-// 3-row stacked operand.  All four kernels are bandwidth kernels: 16-byte accesses, one output chunk per thread, grid-stride loops.
+// The spatial glue of a DPT dense-prediction head (vggt/heads/dpt_head.py; the CroCo adapter of mast3r/catmlp_dpt_head.py) around gd_gemm_nt: every grid
+// is channel-last on the separator-column layout of gd_stack3_rows, [frames, gh * (gw + 1), C], so that each 3x3 convolution of the head is one GEMM on
+// the overlapping-row view of a 3-row stacked operand.  All five kernels are bandwidth kernels with 16-byte accesses and grid-stride loops: one output
+// chunk per thread, except gd_mast3r_head_out, where sixteen lanes share a pixel.
 #include "gd_common.h"
 
 static inline int dpt_blocks(long total) { long b = (total + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
@@ -233,6 +234,123 @@ extern "C" int gd_dpt_head_out(const float* x, const float* w, const float* bias
     GD_REQUIRE(x && w && bias && preds && conf && ((uintptr_t)x & 15) == 0, "gd_dpt_head_out: null pointer, or x not 16-byte aligned");
     hipLaunchKernelGGL(dpt_head_out_kernel, dim3(dpt_blocks((long)frames * H * W)), dim3(256), 0, (hipStream_t)stream, x, w, bias, preds, conf, frames, H, W,
                        Cin, output_dim, act, conf_act);
+    GD_LAUNCH_OK();
+    return 0;
+}
+
+// ---- gd_mast3r_head_out -------------------------------------------------------------------------------------------------------------
+// The MASt3R head's last stage in one pass (mast3r/catmlp_dpt_head.py postprocess / forward, dust3r/heads/postprocess.py): the final 1x1
+// convolution of the DPT adapter on the pitched rectified map, the pixel shuffle of the local-feature MLP's token rows (by addressing alone:
+// lf columns are packed (i, j, c)), and every per-pixel activation.  MH_LANES lanes share one pixel: each takes 16-byte pieces of the Cin row
+// (a wave's loads cover four whole contiguous rows), the od dot products and the descriptor's squared norm are reduced within the group by
+// __shfl_xor (ds_bpermute: no LDS memory, and a handful of values per pixel beside the row stream), and the same lanes read and write the
+// pixel's contiguous D + two_confs values.  expf / expm1f, not the fast intrinsics.
+#define MH_LANES 16
+#define MH_MAX_D 32
+struct Mast3rHeadArgs {
+    int frames, H, W, Cin, od, P, D, two_confs, pts_mode, conf_mode, desc_mode, dconf_mode;
+    float conf_vmin, conf_vmax, dconf_vmin, dconf_vmax;
+};
+__device__ __forceinline__ float mh_group_sum(float v) {
+#pragma unroll
+    for (int m = MH_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ float mh_conf(float y, int mode, float vmin, float vmax) {
+    if (mode == GD_MH_CONF_EXP) {
+        const float e = expf(y), lim = vmax - vmin;
+        return vmin + (e > lim ? lim : e);                       // (a NaN stays a NaN, as torch's clip)
+    }
+    if (mode == GD_MH_CONF_SIGMOID) return (vmax - vmin) * dpt_sigmoid(y) + vmin;
+    return y;
+}
+__global__ __launch_bounds__(256) void mast3r_head_out_kernel(const float* x, const float* w, const float* bias, const float* lf, float* pts3d, float* conf,
+                                                              float* desc, float* desc_conf, Mast3rHeadArgs a) {
+    constexpr int PPB = 256 / MH_LANES;                           // pixels per block and pass
+    const int lane = threadIdx.x % MH_LANES, n = a.D + a.two_confs;
+    const long total = (long)a.frames * a.H * a.W;
+    for (long base = (long)blockIdx.x * PPB; base < total; base += (long)gridDim.x * PPB) {      // block-uniform trips: every lane reaches the shuffles
+        const long p = base + threadIdx.x / MH_LANES;
+        const bool valid = p < total;
+        const long fy = valid ? p / a.W : 0;                      // frame * H + y
+        const int px = valid ? (int)(p - fy * a.W) : 0;
+        float y[4] = {0.f, 0.f, 0.f, 0.f};
+        if (valid) {
+            const float* row = x + (fy * (a.W + 1) + px) * a.Cin;
+            for (int c = lane * 4; c < a.Cin; c += MH_LANES * 4) {
+                float v[4], wv[4];
+                dpt_load<float, 4>(row + c, v);
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (o < a.od) {
+                        dpt_load<float, 4>(w + o * a.Cin + c, wv);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) y[o] = fmaf(v[k], wv[k], y[o]);
+                    }
+            }
+        }
+        // the pixel's D + two_confs <= 33 local-feature values: lane l holds elements l, l + MH_LANES and l + 2 MH_LANES
+        float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+        if (valid && lf) {
+            const int yy = (int)(fy % a.H), gh = a.H / a.P, gw = a.W / a.P;
+            const long trow = ((fy / a.H) * gh + yy / a.P) * gw + px / a.P;
+            const float* src = lf + trow * ((long)a.P * a.P * n) + (long)((yy % a.P) * a.P + px % a.P) * n;
+            if (lane < n) f0 = src[lane];
+            if (lane + MH_LANES < n) f1 = src[lane + MH_LANES];
+            if (lane + 2 * MH_LANES < n) f2 = src[lane + 2 * MH_LANES];
+        }
+        const float s0 = lane < a.D ? f0 * f0 : 0.f, s1 = lane + MH_LANES < a.D ? f1 * f1 : 0.f;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) y[o] = mh_group_sum(y[o]);
+        const float nrm2 = mh_group_sum(s0 + s1);
+        const float extra = __shfl(a.D < MH_LANES ? f0 : a.D < 2 * MH_LANES ? f1 : f2, a.D % MH_LANES, MH_LANES);      // element D: the second confidence's logit
+        if (!valid) continue;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) y[o] += o < a.od ? bias[o] : 0.f;
+        if (lane < 3) {
+            float r = y[lane];
+            if (a.pts_mode != GD_MH_PTS_LINEAR) {
+                const float d = sqrtf(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
+                r = r / fmaxf(d, 1e-8f) * (a.pts_mode == GD_MH_PTS_SQUARE ? d * d : expm1f(d));
+            }
+            pts3d[p * 3 + lane] = r;
+        }
+        const float cv = a.od == 4 ? mh_conf(y[3], a.conf_mode, a.conf_vmin, a.conf_vmax) : 0.f;
+        if (lane == 3 && a.od == 4) conf[p] = cv;
+        if (lf) {
+            const float nrm = a.desc_mode == GD_MH_DESC_NORM ? sqrtf(nrm2) : 1.0f;          // no epsilon, as the reference: a zero vector gives NaN
+            if (lane < a.D) desc[p * a.D + lane] = f0 / nrm;
+            if (lane + MH_LANES < a.D) desc[p * a.D + lane + MH_LANES] = f1 / nrm;
+            if (lane == 4) desc_conf[p] = a.two_confs ? mh_conf(extra, a.dconf_mode, a.dconf_vmin, a.dconf_vmax) : cv;
+        }
+    }
+}
+
+extern "C" int gd_mast3r_head_out(const float* x, const float* w, const float* bias, const float* lf, float* pts3d, float* conf, float* desc,
+                                  float* desc_conf, int frames, int H, int W, int Cin, int od, int P, int D, int two_confs, int pts_mode, int conf_mode,
+                                  float conf_vmin, float conf_vmax, int desc_mode, int dconf_mode, float dconf_vmin, float dconf_vmax, void* stream) {
+    GD_REQUIRE(frames > 0 && H > 0 && W > 0 && Cin > 0, "gd_mast3r_head_out: bad shape frames=%d %dx%d C_in=%d", frames, H, W, Cin);
+    GD_REQUIRE(Cin % 8 == 0, "gd_mast3r_head_out: C_in = %d is not a multiple of 8 (the map's rows are moved in 16-byte pieces)", Cin);
+    GD_REQUIRE(od == 3 || od == 4, "gd_mast3r_head_out: %d output channels: served are 3 (pts3d) and 4 (pts3d + confidence)", od);
+    GD_REQUIRE(pts_mode >= GD_MH_PTS_LINEAR && pts_mode <= GD_MH_PTS_EXP, "gd_mast3r_head_out: unknown pts3d mode code %d", pts_mode);
+    GD_REQUIRE(conf_mode >= GD_MH_CONF_EXP && conf_mode <= GD_MH_CONF_RAW, "gd_mast3r_head_out: unknown confidence mode code %d", conf_mode);
+    GD_REQUIRE((long)frames * H * (W + 1) < (1L << 31), "gd_mast3r_head_out: pixel rows reach 2^31");
+    if (lf) {
+        GD_REQUIRE(P >= 1 && P <= 16, "gd_mast3r_head_out: patch size %d: served are 1 .. 16", P);
+        GD_REQUIRE(D >= 1 && D <= MH_MAX_D, "gd_mast3r_head_out: %d descriptor channels: served are 1 .. %d", D, MH_MAX_D);
+        GD_REQUIRE(two_confs == 0 || two_confs == 1, "gd_mast3r_head_out: two_confs = %d: 0 or 1", two_confs);
+        GD_REQUIRE(H % P == 0 && W % P == 0, "gd_mast3r_head_out: the %dx%d map is not a whole number of %d-pixel patches", H, W, P);
+        GD_REQUIRE(two_confs || od == 4, "gd_mast3r_head_out: without two_confs desc_conf copies conf, which a 3-channel head does not have");
+        GD_REQUIRE(desc_mode == GD_MH_DESC_NORM || desc_mode == GD_MH_DESC_RAW, "gd_mast3r_head_out: unknown descriptor mode code %d", desc_mode);
+        GD_REQUIRE(dconf_mode >= GD_MH_CONF_EXP && dconf_mode <= GD_MH_CONF_RAW, "gd_mast3r_head_out: unknown desc_conf mode code %d", dconf_mode);
+    }
+    GD_REQUIRE(x && w && bias && pts3d && (od == 3 || conf) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0,
+               "gd_mast3r_head_out: null pointer (x, w, bias, pts3d, conf with 4 channels), or x / w not 16-byte aligned");
+    GD_REQUIRE(!lf || (desc && desc_conf && ((uintptr_t)lf & 15) == 0), "gd_mast3r_head_out: desc / desc_conf null, or lf not 16-byte aligned");
+    Mast3rHeadArgs a{frames, H, W, Cin, od, lf ? P : 1, lf ? D : 0, lf ? two_confs : 0, pts_mode, conf_mode, desc_mode, dconf_mode,
+                     conf_vmin, conf_vmax, dconf_vmin, dconf_vmax};
+    hipLaunchKernelGGL(mast3r_head_out_kernel, dim3(dpt_blocks((long)frames * H * W * MH_LANES)), dim3(256), 0, (hipStream_t)stream, x, w, bias, lf, pts3d,
+                       conf, desc, desc_conf, a);
     GD_LAUNCH_OK();
     return 0;
 }

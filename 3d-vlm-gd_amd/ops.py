@@ -936,6 +936,41 @@ def dpt_head_out(x, w, bias, frames, H, W, activation, conf_activation):
     return preds, conf
 
 
+MH_PTS = {"linear": 0, "square": 1, "exp": 2}                 # include/gd_hip.h GD_MH_PTS_* ("linear": the value before the activation)
+MH_CONF = {"exp": 0, "sigmoid": 1, "raw": 2}                  # GD_MH_CONF_*
+MH_DESC = {"norm": 0, "raw": 1}                               # GD_MH_DESC_*
+
+
+def mast3r_head_out(x, w, bias, lf, frames, H, W, *, patch=16, desc_dim=0, two_confs=False, pts_mode="linear", conf_mode=("raw", 0.0, 0.0),
+                    desc_mode="norm", desc_conf_mode=("raw", 0.0, 0.0)):
+    """x: pitched [frames*H*(W+1), Cin] fp32, w [od, Cin], bias [od] (od = 3 | 4), lf: None or token rows [frames*(H/patch)*(W/patch),
+    patch*patch*(desc_dim + two_confs)] fp32 with columns packed (i, j, c) -> (pts3d [frames, H, W, 3], conf [frames, H, W] or None when od = 3,
+    desc [frames, H, W, desc_dim], desc_conf [frames, H, W]; the last two None without lf) (gd_mast3r_head_out).  conf_mode, desc_conf_mode:
+    (mode, vmin, vmax)."""
+    _req(pts_mode in MH_PTS, f"mast3r_head_out: pts3d mode {pts_mode!r}: served are {sorted(MH_PTS)}")
+    _req(conf_mode[0] in MH_CONF, f"mast3r_head_out: conf mode {conf_mode[0]!r}: served are {sorted(MH_CONF)}")
+    _req(desc_conf_mode[0] in MH_CONF, f"mast3r_head_out: desc_conf mode {desc_conf_mode[0]!r}: served are {sorted(MH_CONF)}")
+    _req(desc_mode in MH_DESC, f"mast3r_head_out: desc mode {desc_mode!r}: served are {sorted(MH_DESC)}")
+    _req(w.dim() == 2, "mast3r_head_out: w is [od, Cin]")
+    od, Cin = w.shape
+    _req(all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (x, w, bias)) and tuple(x.shape) == (frames * H * (W + 1), Cin) and
+         bias.numel() == od, "mast3r_head_out: bad x / w / bias")
+    tc = 1 if two_confs else 0
+    pts3d = torch.empty(frames, H, W, 3, dtype=torch.float32, device=x.device)
+    conf = torch.empty(frames, H, W, dtype=torch.float32, device=x.device) if od == 4 else None
+    desc = desc_conf = None
+    if lf is not None:
+        _req(patch >= 1 and H % patch == 0 and W % patch == 0 and desc_dim >= 1, "mast3r_head_out: H, W must be multiples of patch, desc_dim >= 1")
+        _req(lf.is_cuda and lf.dtype == torch.float32 and lf.is_contiguous() and
+             tuple(lf.shape) == (frames * (H // patch) * (W // patch), patch * patch * (desc_dim + tc)), "mast3r_head_out: bad lf")
+        desc = torch.empty(frames, H, W, desc_dim, dtype=torch.float32, device=x.device)
+        desc_conf = torch.empty(frames, H, W, dtype=torch.float32, device=x.device)
+    check(lib().gd_mast3r_head_out(ptr(x), ptr(w), ptr(bias), ptr(lf), ptr(pts3d), ptr(conf), ptr(desc), ptr(desc_conf), frames, H, W, Cin, od, int(patch),
+                                   int(desc_dim), tc, MH_PTS[pts_mode], MH_CONF[conf_mode[0]], float(conf_mode[1]), float(conf_mode[2]), MH_DESC[desc_mode],
+                                   MH_CONF[desc_conf_mode[0]], float(desc_conf_mode[1]), float(desc_conf_mode[2]), stream()), "gd_mast3r_head_out")
+    return pts3d, conf, desc, desc_conf
+
+
 class _TapMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prefix, with_norm, *grids):

@@ -201,16 +201,25 @@ class MASt3RTeacherRunner:
     is the faithful mode, the reference runs this teacher in fp32; torch.bfloat16 is narrower and faster).  For the duration of `targets()`
     only, instance attributes shadow `matcher._decoder` (by FusedCroCoBlocks.decode) and every `enc_blocks[i].forward` (the first runs the whole
     stack, the others return their input), so the user's own `forward` — patch embedding, `enc_norm`, heads — drives the fused path.  The
-    shadowed `_decoder` returns one-head head-mean score maps [B, 1, Nq, Nk], which `forward`'s and this class's `.mean(dim=1)` leave unchanged."""
+    shadowed `_decoder` returns one-head head-mean score maps [B, 1, Nq, Nk], which `forward`'s and this class's `.mean(dim=1)` leave unchanged.
+
+    fused_heads: `downstream_head1` and `downstream_head2` run on the HIP kernels (teacher_heads.FusedMASt3RHead, operand type `heads_dtype`:
+    torch.float32 is the faithful mode, the reference runs its heads in fp32 with autocast off).  Independent of `fused_blocks`; a head the class
+    does not serve raises here, naming the attribute.  For the duration of `targets()` only, an instance attribute shadows each module's `forward`,
+    so the `head1` / `head2` closures the matcher built around those modules (portrait / landscape handling) keep driving the fused path."""
 
     def __init__(self, matcher, inference=None, make_pairs=None, min_conf_thr=10, subsample=16, keep_logits=False, fused_blocks=False,
-                 dtype=torch.float32):
+                 dtype=torch.float32, fused_heads=False, heads_dtype=torch.float32):
         self.matcher, self.inference, self.make_pairs = matcher, inference, make_pairs
         self.min_conf_thr, self.subsample, self.keep_logits = min_conf_thr, subsample, keep_logits
         self.fused = None
         if fused_blocks:
             from .teacher_blocks import FusedCroCoBlocks
             self.fused = FusedCroCoBlocks(matcher, dtype=dtype)
+        self.heads = None
+        if fused_heads:
+            from . import teacher_heads
+            self.heads = {n: teacher_heads.FusedMASt3RHead(getattr(matcher, n), dtype=heads_dtype, name=n) for n in ("downstream_head1", "downstream_head2")}
 
     @torch.no_grad()
     def targets(self, rgb_mast3r_1, rgb_mast3r_2, temperature=1.0, intrinsic=None, depth_1=None, depth_2=None, device="cuda"):
@@ -243,6 +252,8 @@ class MASt3RTeacherRunner:
             if fused is not None:
                 for i, blk in enumerate(self.matcher.enc_blocks):
                     shadow(blk, "forward", fused.encode if i == 0 else (lambda x, pos=None: x))
+            for n, head in (self.heads or {}).items():
+                shadow(getattr(self.matcher, n), "forward", head.forward)
             out = inf(mk([rgb_mast3r_1, rgb_mast3r_2], scene_graph="complete", prefilter=None, symmetrize=True), self.matcher, device,
                       verbose=False)
         finally:

@@ -198,6 +198,27 @@ int gd_deconv_scatter(const float* src, const float* bias, float* dst, int frame
 #define GD_DPT_CONF_LINEAR 3     /* y itself: the pre-activation map */
 int gd_dpt_head_out(const float* x, const float* w, const float* bias, float* preds, float* conf, int frames, int H, int W, int Cin, int output_dim,
                     int act, int conf_act, void* stream);
+/* The MASt3R head's last stage in one pass — what mast3r/catmlp_dpt_head.py `forward` (pixel shuffle, concatenation) and `postprocess` with
+ * dust3r/heads/postprocess.py reg_dense_depth / reg_dense_conf compute after the DPT adapter's last ReLU and the local-feature MLP's fc2.
+ * x: the pitched rectified map [frames * H * (W + 1), C_in] (f32), w [od, C_in], bias [od] of the final 1x1 convolution, od = 3 | 4 (3 + has_conf).
+ * lf: fc2's output as token rows [frames * (H/P) * (W/P), P * P * (D + two_confs)] (f32) whose columns are packed (i, j, c) — a pixel's D + two_confs
+ * values are contiguous, F.pixel_shuffle(., P) is addressing alone — or null for a pts3d-only head (desc, desc_conf, P, D, two_confs then unused).
+ * -> pts3d [frames, H, W, 3], conf [frames, H, W] (od = 4; unused with od = 3), desc [frames, H, W, D], desc_conf [frames, H, W]: f32, no separators.
+ * pts3d: LINEAR xyz itself (the value before the activation); else d = |xyz|, u = xyz / max(d, 1e-8): SQUARE u d^2, EXP u expm1(d).
+ * conf, desc_conf (mode, vmin, vmax): EXP vmin + min(exp(y), vmax - vmin) (vmax may be +inf), SIGMOID (vmax - vmin) sigmoid(y) + vmin, RAW y.
+ * With two_confs = 0, desc_conf is a copy of conf (od = 4 required).  desc: NORM v / |v| over the D channels with NO epsilon, as the reference — a
+ * zero vector gives NaN there too; RAW v.  C_in a multiple of 8, 1 <= P <= 16, 1 <= D <= 32, H and W multiples of P, x, w, lf 16-byte aligned. */
+#define GD_MH_PTS_LINEAR 0
+#define GD_MH_PTS_SQUARE 1
+#define GD_MH_PTS_EXP 2
+#define GD_MH_CONF_EXP 0
+#define GD_MH_CONF_SIGMOID 1
+#define GD_MH_CONF_RAW 2
+#define GD_MH_DESC_NORM 0
+#define GD_MH_DESC_RAW 1
+int gd_mast3r_head_out(const float* x, const float* w, const float* bias, const float* lf, float* pts3d, float* conf, float* desc, float* desc_conf,
+                       int frames, int H, int W, int Cin, int od, int P, int D, int two_confs, int pts_mode, int conf_mode, float conf_vmin,
+                       float conf_vmax, int desc_mode, int dconf_mode, float dconf_vmin, float dconf_vmax, void* stream);
 /* interpolate_features (utils/functions.py:55-76) on 1..4 token-major grids, averaged; backward scatters into fp32
  * gradient grids (batch stride bstride elements, pre-zeroed).  pitch = tokens per grid line in memory (gw for a dense grid,
  * gw + 1 for the separator-column layout of gd_stack3_rows' GEMM output). */

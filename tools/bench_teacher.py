@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -25,6 +25,11 @@
    "vggt_dpt_heads_share_of_targets" (--sections heads_share): a VGGT-shaped random-weight teacher (the aggregator at --depth / --width with fused_blocks, depth and
    point heads, a track head whose feature extractor is a 128-feature head at down_ratio 2 around a stub tracker): the three heads' time, on the
    modules and fused, beside `aggregate` and the whole `targets()` call.
+6. "mast3r_heads" (--sections mast3r_heads): ONE head of the MASt3R teacher at its size — encoder width 1024, decoder width 768, 256 features,
+   last_dim 128, 24 descriptor channels, two_confs, two frames of 384 x 512 (a 24 x 32 token grid), random weights: teacher_heads.FusedMASt3RHead
+   (f32 and bf16 operands) against the torch module of tests/mast3r_head_layout.py (f32, and under bf16 autocast), measured as section 5 is.
+   "mast3r_heads_share" (--sections mast3r_heads_share): a MASt3R-shaped random-weight teacher (the transformer of section 4 with fused_blocks in
+   bf16, a linear patch embedding, two such heads): `targets()` of one pair and the two heads alone, on the modules and with fused_heads (f32, bf16).
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -95,10 +100,15 @@ def main():
         dpt_head_section(res, a, dev)
     if "heads_share" in sections:
         dpt_share_section(res, a, dev)
+    if "mast3r_heads" in sections:
+        mast3r_head_section(res, a, dev)
+    if "mast3r_heads_share" in sections:
+        mast3r_share_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
-           "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"]}
+           "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
+           "mast3r_heads_share": ["mast3r_heads_share"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -198,6 +208,94 @@ def dpt_share_section(res, a, dev):
         out[tag]["heads_share_of_targets"] = round(out[tag]["three_heads"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
         del r
     res["vggt_dpt_heads_share_of_targets"] = out
+
+
+MAST3R_HEAD = dict(enc_dim=1024, dec_dim=768, feature_dim=256, last_dim=128, local_feat_dim=24, two_confs=True)
+MAST3R_IMG = (384, 512)
+
+
+def mast3r_head_section(res, a, dev):
+    import mast3r_head_layout as ML
+    from gd_amd.teacher_heads import FusedMASt3RHead
+    B, (H, W) = 2, MAST3R_IMG
+    N = (H // 16) * (W // 16)
+    with torch.device(dev):
+        m = ML.MASt3RHeadLayout(**MAST3R_HEAD).eval()
+    decout = [torch.randn(B, N, MAST3R_HEAD["enc_dim"] if i == 0 else MAST3R_HEAD["dec_dim"], device=dev) for i in range(ML.DEC_DEPTH + 1)]
+    f32, bf = FusedMASt3RHead(m, dtype=torch.float32), FusedMASt3RHead(m, dtype=torch.bfloat16)
+
+    def module_run(autocast, taps=None):
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            return m(decout, (H, W), taps=taps)
+    paths = {"fused_f32": lambda: f32(decout, (H, W)), "module_f32": lambda: module_run(False), "fused_bf16": lambda: bf(decout, (H, W)),
+             "module_bf16_autocast": lambda: module_run(True)}
+    out = dict(MAST3R_HEAD, frames=B, image=[H, W], patch_grid=[H // 16, W // 16], hooks=ML.HOOKS, layer_dims=list(ML.LAYER_DIMS))
+    prof = ops.GemmProfiler()
+    ops.set_gemm_profiler(prof)
+    f32(decout, (H, W))
+    ops.set_gemm_profiler(None)
+    flop, _, launches = prof.totals()
+    mlp = prof.totals(keep=lambda tag: tag[1] in (m.head_local_features.fc1.out_features, m.head_local_features.fc2.out_features) and tag[0] == B * N)[0]
+    out["fused_gemm_flop"], out["fused_gemm_launches"], out["fused_gemm_flop_mlp"] = flop, launches, mlp
+    for name in ("fused_f32", "fused_bf16", "module_f32", "module_bf16_autocast"):
+        paths[name]()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        paths[name]()
+        torch.cuda.synchronize()
+        out[name + "_peak_workspace_MB"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+    # each path twice, interleaved: other work shares the machine
+    for name, fn in paths.items():
+        out[name] = timed(fn, a.warm, a.iters)
+    for name, fn in paths.items():
+        out[name + "_again"] = timed(fn, 1, a.iters)
+    best = lambda k: min(out[k]["median_ms"], out[k + "_again"]["median_ms"])
+    out["speedup_fused_f32_vs_module_f32"] = round(best("module_f32") / best("fused_f32"), 3)
+    out["speedup_fused_bf16_vs_module_bf16_autocast"] = round(best("module_bf16_autocast") / best("fused_bf16"), 3)
+    out["fused_f32_tflops"] = round(flop / best("fused_f32") * 1e-9, 1)
+    out["fused_bf16_tflops"] = round(flop / best("fused_bf16") * 1e-9, 1)
+    tf, tm, tb, ta = {}, {}, {}, {}
+    f32(decout, (H, W), taps=tf), module_run(False, tm), bf(decout, (H, W), taps=tb), module_run(True, ta)
+    rel = lambda x, y: float((x.float() - y).abs().max() / y.abs().max())
+    out["pre_activation_rel_diff_vs_module_f32"] = {"fused_f32": rel(tf["pre"], tm["pre"]), "fused_bf16": rel(tb["pre"], tm["pre"]),
+                                                    "module_bf16_autocast": rel(ta["pre"], tm["pre"])}
+    res["mast3r_heads"] = out
+
+
+def mast3r_share_section(res, a, dev):
+    import mast3r_head_layout as ML
+    from gd_amd.teacher_runner import MASt3RTeacherRunner
+    (H, W), B = MAST3R_IMG, 2
+    cfg = dict(enc_dim=1024, enc_heads=16, enc_depth=a.depth, dec_dim=768, dec_heads=12, dec_depth=a.depth // 2, temperature=3.0, reciprocity=True)
+    head_kw = {k: v for k, v in MAST3R_HEAD.items() if k not in ("enc_dim", "dec_dim")}
+    with torch.device(dev):
+        m = ML.tiny_matcher(cfg, (H, W), dict(head_kw, layer_dims=ML.LAYER_DIMS), fill=False)
+    img1, img2 = torch.rand(1, 3, H, W, device=dev), torch.rand(1, 3, H, W, device=dev)
+    depth = torch.rand(H, W, device=dev) + 1.0
+    N = (H // 16) * (W // 16)
+    decout = [torch.randn(B, N, cfg["enc_dim"] if i == 0 else cfg["dec_dim"], device=dev) for i in range(cfg["dec_depth"] + 1)]
+    out = dict(cfg, image=[H, W], blocks="fused_blocks bf16", head=head_kw)
+    runs = {}
+    for tag, kw in (("module_heads_f32", {}), ("fused_heads_f32", dict(fused_heads=True)), ("fused_heads_bf16", dict(fused_heads=True, heads_dtype=torch.bfloat16))):
+        r = MASt3RTeacherRunner(m, inference=ML.inference, make_pairs=ML.make_pairs, min_conf_thr=0, fused_blocks=True, dtype=torch.bfloat16, **kw)
+        hs = list(r.heads.values()) if r.heads else [m.downstream_head1, m.downstream_head2]
+
+        def heads_run(hs=hs):
+            with torch.no_grad():
+                for h in hs:
+                    h(decout, (H, W))
+        runs[tag] = (lambda r=r: r.targets(img1, img2, depth_1=depth, depth_2=depth), heads_run)
+        out[tag] = {"targets_returned_none": runs[tag][0]() is None}
+    # each path twice, alternating: other work shares the machine
+    for again in ("", "_again"):
+        for tag, (targets, heads_run) in runs.items():
+            out[tag]["targets" + again] = timed(targets, 1, a.iters)
+            out[tag]["two_heads" + again] = timed(heads_run, 1, a.iters)
+    for tag in runs:
+        best = lambda k: min(out[tag][k]["median_ms"], out[tag][k + "_again"]["median_ms"])
+        out[tag]["heads_share_of_targets"] = round(best("two_heads") / best("targets"), 3)
+    res["mast3r_heads_share"] = out
 
 
 def mast3r_sections(res, a, dev):
