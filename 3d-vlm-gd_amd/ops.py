@@ -1616,3 +1616,120 @@ def track_points(E, feats, frames=None, geometry=None, radius=35, precision="f16
             c[order.to(dev)] = cell
             cell = c
     return (xy, cell.long()) if want_cell else xy
+
+
+# ------------------------------------------------------------------------------------------------ VGGT tracker tail (csrc/vggt_track.hip)
+def _f32c(t, shape, what):
+    _req(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape),
+         f"{what} must be a contiguous CUDA fp32 tensor {tuple(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+def avgpool2_cl(src, W=None, pitch_out=None):
+    """src: a channel-last map [F, H, pitch, 128] fp32 with W <= pitch data columns (default: all of them) -> the next pyramid level
+    [F, H // 2, pitch_out, 128] (gd_avgpool2_cl: 2 x 2 mean, stride 2, odd last row / column dropped); pitch_out defaults to W // 2."""
+    _req(src.dim() == 4, "avgpool2_cl: src must be [F, H, pitch, C]")
+    F, H, pitch, C = src.shape
+    W = pitch if W is None else int(W)
+    _f32c(src, (F, H, pitch, C), "avgpool2_cl: src")
+    _req(2 <= W <= pitch and H >= 2, f"avgpool2_cl: W {W} must be in [2, pitch {pitch}] and H {H} >= 2")
+    po = W // 2 if pitch_out is None else int(pitch_out)
+    _req(po >= W // 2, f"avgpool2_cl: pitch_out {po} < W // 2 = {W // 2}")
+    out = torch.empty(F, H // 2, po, C, dtype=torch.float32, device=src.device)
+    check(lib().gd_avgpool2_cl(ptr(src), ptr(out), F, H, W, pitch, po, C, stream()), "gd_avgpool2_cl")
+    return out
+
+
+def corr_pyramid(fmap, W, levels):
+    """fmap [F, H, pitch, 128] (W <= pitch data columns) -> [(map, H, W, pitch)] of `levels` levels, each pooled from the previous (blocks.py:166-176)."""
+    pyr = [(fmap, fmap.shape[1], int(W), fmap.shape[2])]
+    for _ in range(levels - 1):
+        m, h, w, _p = pyr[-1]
+        _req(h >= 2 and w >= 2, f"corr_pyramid: level {len(pyr) - 1} is {h} x {w}: it cannot be pooled further ({levels} levels asked)")
+        nxt = avgpool2_cl(m, w)
+        pyr.append((nxt, h // 2, w // 2, w // 2))
+    return pyr
+
+
+def corr_sample(pyramid, targets, coords, radius, ld=None):
+    """pyramid: [(map [F, H, pitch, 128], H, W, pitch)] per level (corr_pyramid); targets [B, N, S, 128], coords [B, N, S, 2] (level-0 cells),
+    F = B * S -> [B * S, N, ld] fp32 (gd_corr_sample), ld >= levels * (2 radius + 1)^2 (default: exactly that), the columns beyond written as zeros."""
+    import ctypes
+    _req(targets.dim() == 4 and coords.dim() == 4, "corr_sample: targets [B, N, S, C] and coords [B, N, S, 2]")
+    B, N, S, C = targets.shape
+    _f32c(targets, (B, N, S, C), "corr_sample: targets")
+    _f32c(coords, (B, N, S, 2), "corr_sample: coords")
+    L, r = len(pyramid), int(radius)
+    dims = []
+    for l, (m, h, w, p) in enumerate(pyramid):
+        _f32c(m, (B * S, h, p, C), f"corr_sample: level {l}")
+        _req(w <= p, f"corr_sample: level {l}: W {w} > pitch {p}")
+        dims += [int(h), int(w), int(p)]
+    n = L * (2 * r + 1) ** 2
+    ld = n if ld is None else int(ld)
+    _req(ld >= n, f"corr_sample: ld {ld} < levels * (2r + 1)^2 = {n}")
+    out = torch.empty(B * S, N, ld, dtype=torch.float32, device=targets.device)
+    check(lib().gd_corr_sample(_ptr_array([m for m, _, _, _ in pyramid]), (ctypes.c_int * len(dims))(*dims), L, r, ptr(targets), ptr(coords), B, S, N, C,
+                               ptr(out), ld, stream()), "gd_corr_sample")
+    return out
+
+
+def points_bilinear(fmap, W, points, frame_step=1):
+    """fmap [F, H, pitch, 128] (W data columns), points [B, N, 2] (x, y) in cells -> [B, N, 128]: the bilinear sample (align_corners=True, border
+    clamp) of frame b * frame_step (gd_points_bilinear)."""
+    _req(fmap.dim() == 4 and points.dim() == 3, "points_bilinear: fmap [F, H, pitch, C] and points [B, N, 2]")
+    F, H, pitch, C = fmap.shape
+    B, N, _ = points.shape
+    _f32c(fmap, (F, H, pitch, C), "points_bilinear: fmap")
+    _f32c(points, (B, N, 2), "points_bilinear: points")
+    _req(1 <= W <= pitch and frame_step >= 1 and (B - 1) * frame_step < F, f"points_bilinear: W {W} / pitch {pitch}, or frame {(B - 1) * frame_step} outside the {F} frames")
+    out = torch.empty(B, N, C, dtype=torch.float32, device=fmap.device)
+    check(lib().gd_points_bilinear(ptr(fmap), ptr(points), ptr(out), B, N, H, int(W), pitch, C, int(frame_step), stream()), "gd_points_bilinear")
+    return out
+
+
+def track_pos_omega(D, device):
+    """omega [D / 4] fp32 of get_1d_sincos_pos_embed_from_grid(D / 2, .) (utils.py:79-81), computed in double."""
+    q = D // 4
+    return (1.0 / 10000 ** (torch.arange(q, dtype=torch.float64) / q)).float().to(device)
+
+
+def track_pos_embed(points, H, W, D, omega=None):
+    """points [M, 2] (x, y) in cells -> [M, D]: get_2d_sincos_pos_embed(D, (H, W)) sampled bilinearly with border clamp (gd_track_pos_embed)."""
+    _req(points.dim() == 2 and D % 4 == 0, "track_pos_embed: points [M, 2], D a multiple of 4")
+    M = points.shape[0]
+    _f32c(points, (M, 2), "track_pos_embed: points")
+    omega = track_pos_omega(D, points.device) if omega is None else omega
+    _f32c(omega, (D // 4,), "track_pos_embed: omega")
+    out = torch.empty(M, D, dtype=torch.float32, device=points.device)
+    check(lib().gd_track_pos_embed(ptr(points), ptr(omega), ptr(out), M, int(H), int(W), int(D), stream()), "gd_track_pos_embed")
+    return out
+
+
+def track_assemble(coords, corr, feats, pos, ref_token, max_scale):
+    """coords [B, N, S, 2], corr [B, S, N, C] (corr_mlp's rows), feats [B, N, S, C], pos [B * N, 3C + 4], ref_token [2, 3C + 4] ->
+    the update transformer's input [B, N, S, 3C + 4] (gd_track_assemble)."""
+    _req(feats.dim() == 4, "track_assemble: feats [B, N, S, C]")
+    B, N, S, C = feats.shape
+    D = 3 * C + 4
+    for t, shape, what in ((coords, (B, N, S, 2), "coords"), (corr, (B, S, N, C), "corr"), (feats, (B, N, S, C), "feats"), (pos, (B * N, D), "pos"),
+                           (ref_token, (2, D), "ref_token")):
+        _f32c(t, shape, f"track_assemble: {what}")
+    x = torch.empty(B, N, S, D, dtype=torch.float32, device=feats.device)
+    check(lib().gd_track_assemble(ptr(coords), ptr(corr), ptr(feats), ptr(pos), ptr(ref_token), ptr(x), B, S, N, C, float(max_scale), stream()),
+          "gd_track_assemble")
+    return x
+
+
+def track_update(delta, coords, mul1=1.0, mul2=1.0):
+    """delta [B, N, S, C + 2] (last dim contiguous, equal row strides), coords [B, N, S, 2] (updated IN PLACE for s > 0) ->
+    (pred [B, S, N, 2] = (coords * mul1) * mul2, dfeat [B * N * S, C] = delta[..., 2:]) (gd_track_update)."""
+    _req(delta.dim() == 4 and coords.dim() == 4, "track_update: delta [B, N, S, C + 2] and coords [B, N, S, 2]")
+    B, N, S, C2 = delta.shape
+    C = C2 - 2
+    _f32c(coords, (B, N, S, 2), "track_update: coords")
+    d = delta.reshape(B * N * S, C2) if delta.is_contiguous() else delta.contiguous().view(B * N * S, C2)
+    _req(d.is_cuda and d.dtype == torch.float32, "track_update: delta must be a CUDA fp32 tensor")
+    pred = torch.empty(B, S, N, 2, dtype=torch.float32, device=d.device)
+    dfeat = torch.empty(B * N * S, C, dtype=torch.float32, device=d.device)
+    check(lib().gd_track_update(ptr(d), d.stride(0), ptr(coords), ptr(pred), ptr(dfeat), B, S, N, C, float(mul1), float(mul2), stream()), "gd_track_update")
+    return pred, dfeat

@@ -312,8 +312,9 @@ class FusedDPTHead(_FusedHead):
             self._tables[key] = (px.contiguous(), py.contiguous(), rows)
         return self._tables[key]
 
-    def _frame(self, toks, gh, gw, img_hw, taps):
-        """One frame: toks the four [gh*gw, dim_in] token-row views -> (preds [1, H, W, od-1], conf [1, H, W]) or features [C, H', W']."""
+    def _frame(self, toks, gh, gw, img_hw, taps, channel_last=False):
+        """One frame: toks the four [gh*gw, dim_in] token-row views -> (preds [1, H, W, od-1], conf [1, H, W]) or features [C, H', W']
+        (channel_last: the pitched grid itself, [H', W' + 1, C])."""
         dt, C, dev = self.dtype, self.features, toks[0].device
         aspect = img_hw[1] / img_hw[0]
         sizes, skips = [], []
@@ -335,7 +336,8 @@ class FusedDPTHead(_FusedHead):
         if self.feature_only:
             if taps is not None:
                 taps.setdefault("pre", []).append(fused.view(h, w_ + 1, C1)[:, :w_].permute(2, 0, 1))
-            return ops.grid_resample(fused, 1, h, w_, th, tw, C1, px=px, py=py).view(th, tw + 1, C1)[:, :tw].permute(2, 0, 1)
+            grid = ops.grid_resample(fused, 1, h, w_, th, tw, C1, px=px, py=py).view(th, tw + 1, C1)
+            return grid if channel_last else grid[:, :tw].permute(2, 0, 1)
         hid = self._conv3(ops.grid_resample(fused, 1, h, w_, th, tw, C1, px=px, py=py, stacked=dt), th, tw, C1, self.out2, act=2)
         if taps is not None:
             v, c = ops.dpt_head_out(hid, self.w_last, self.b_last, 1, th, tw, "linear", "linear")
@@ -343,11 +345,15 @@ class FusedDPTHead(_FusedHead):
         return ops.dpt_head_out(hid, self.w_last, self.b_last, 1, th, tw, self.activation, self.conf_activation)
 
     @torch.no_grad()
-    def forward(self, aggregated_tokens_list, images, patch_start_idx, frames_chunk_size=None, taps=None):
+    def forward(self, aggregated_tokens_list, images, patch_start_idx, frames_chunk_size=None, taps=None, channel_last=False):
         """Same signature and result as the module's forward.  Frames are independent and always run one at a time (at the teacher's size the fp32
         operand of the last convolution is ~410 MB per frame), so `frames_chunk_size` changes neither the result nor the peak memory.
         taps: a dict that receives "pre" — the map before the activations [B*S, output_dim, H, W], or with feature_only the fused map before the
-        last resampling (what the tests compare with the reference's)."""
+        last resampling (what the tests compare with the reference's).
+        channel_last (feature_only heads): -> (features [B, S, H', W', C], pitch): the data columns of the pitched grids [B, S, H', pitch = W' + 1, C]
+        the head works on, without the permutation to [B, S, C, H', W'] (what teacher_tracker.FusedTracker takes as `fmaps_cl`)."""
+        if channel_last and not self.feature_only:
+            raise GdHipError(f"FusedDPTHead: {self.name}: channel_last is served for feature_only heads")
         B, S, _, H, W = images.shape
         gh, gw = H // self.patch, W // self.patch
         outs = []
@@ -360,11 +366,13 @@ class FusedDPTHead(_FusedHead):
                         raise GdHipError(f"FusedDPTHead: {self.name}: aggregated_tokens_list[{li}] {tuple(t.shape)} on {t.device} does not hold a "
                                          f"{gh} x {gw} patch grid after {patch_start_idx} prefix tokens on the GPU")
                     toks.append(t[b, s, patch_start_idx:])
-                outs.append(self._frame(toks, gh, gw, (H, W), taps))
+                outs.append(self._frame(toks, gh, gw, (H, W), taps, channel_last))
         if taps is not None:
             taps["pre"] = torch.stack(taps["pre"])
         if self.feature_only:
             f = torch.stack(outs)
+            if channel_last:
+                return f.view(B, S, *f.shape[1:])[:, :, :, :-1], f.shape[2]
             return f.view(B, S, *f.shape[1:])
         preds, conf = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
         return preds.view(B, S, *preds.shape[1:]), conf.view(B, S, *conf.shape[1:])

@@ -11,7 +11,8 @@ PyTorch-ROCm inference).  What lives here is the glue around them:
 * `VGGTTeacherRunner` — `extract_vggt_features` + `sample_keypoints` (src/finetune_timm_vggt.py:357-449) as one call that returns the
   pair's targets in the cache layout; the reference aggregator's hard-wired `return_attn=True` is neutralised for the duration of the
   call (the selected blocks return a 1-element placeholder instead of the maps); with `fused_heads` the three dense-prediction heads run on
-  the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules;
+  the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules, and with `fused_tracker` the tracker's tail runs on
+  teacher_tracker.FusedTracker;
 * `MASt3RTeacherRunner` — `extract_mast3r_features` + `filter_and_match_keypoints` + the depth branch
   (src/finetune_timm_mast3r.py:345-469, 617-633) around the user's `dust3r.inference.inference`.
 """
@@ -101,7 +102,8 @@ class VGGTTeacherRunner:
     `temperature`; camera_head, depth_head, point_head, track_head).  `pose_decoder(pose_enc, image_hw) -> (extrinsic, intrinsic)`
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
-    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32):
+    def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32,
+                 fused_tracker=False):
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
         agg = vggt.aggregator
         per = getattr(agg, "aa_block_size", 1)
@@ -119,6 +121,13 @@ class VGGTTeacherRunner:
             from .teacher_heads import FusedDPTHead
             self.heads = {n: FusedDPTHead(h, dtype=heads_dtype, name=n) for n, h in (("depth_head", vggt.depth_head), ("point_head", vggt.point_head),
                                                                                       ("track_head.feature_extractor", vggt.track_head.feature_extractor))}
+        # fused_tracker: the tracker's correlation pyramid, window sampling, position embedding, glue and small MLPs run on the HIP kernels
+        # (teacher_tracker.FusedTracker, fp32; the update transformer stays the user's module).  Independent of fused_blocks and fused_heads; a tracker the
+        # class refuses raises here, not in targets().
+        self.tracker = None
+        if fused_tracker:
+            from .teacher_tracker import FusedTracker
+            self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker")
 
     def _block_inputs(self, rgb_vggt):
         """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the
@@ -175,6 +184,15 @@ class VGGTTeacherRunner:
         _, point_conf = (heads["point_head"] if heads else m.point_head)(tokens_list, rgb_vggt, ps_idx)
 
         def track(kp1):
+            if self.tracker is not None:
+                # the feature extractor's map goes straight to the fused tracker: channel-last from the fused head, NCHW from the user's
+                iters = int(getattr(m.track_head, "iters", 4))
+                if heads:
+                    fm, pitch = heads["track_head.feature_extractor"](tokens_list, rgb_vggt, ps_idx, channel_last=True)
+                    trk, _, _ = self.tracker(kp1[None], iters=iters, fmaps_cl=fm, pitch=pitch)
+                else:
+                    trk, _, _ = self.tracker(kp1[None], m.track_head.feature_extractor(tokens_list, rgb_vggt, ps_idx), iters=iters)
+                return trk[-1][0][1]
             # with fused heads, for this call only, an instance attribute shadows the feature extractor's forward: the user's track_head drives the fused head
             fe = m.track_head.feature_extractor if heads else None
             if fe is not None:

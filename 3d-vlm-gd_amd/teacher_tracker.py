@@ -1,0 +1,284 @@
+"""The VGGT teacher's tracker tail (vggt/heads/track_modules/base_track_predictor.py:82-209 BaseTrackerPredictor.forward) on the HIP kernels of
+csrc/vggt_track.hip and the existing GEMM / LayerNorm entry points, instead of the user's PyTorch module.
+
+What the reference does in every iteration and this class does not:
+  * it rebuilds the [1, 388, H, W] sin/cos position table on the host and copies it over (:149) to sample it at N points (:150) —
+    here gd_track_pos_embed computes the N sampled rows once per call;
+  * it writes the full correlation volume of every pyramid level (blocks.py:205-246) to read (2r+1)^2 values per point from it —
+    here gd_corr_sample computes the (2r+2)^2 dot products a window needs and blends them; the volume never exists;
+  * it permutes the feature map NCHW -> NHWC -> NCHW around `fmap_norm` (:94-95) — here every map is channel-last (`fmaps_cl=` takes the fused
+    DPT head's map as it is, separator column included).
+
+One iteration (`step`) is
+    corr_sample -> gemm_nt(+bias, GELU) -> gemm_nt(+bias)            (the window samples, `corr_mlp`)
+    track_assemble                                                    (flow embedding | flow / max_scale | corr | track_feats, + position + query token)
+    updateformer                                                      (the USER'S module, called as it stands)
+    track_update                                                      (coords += delta[:2], frame 0 pinned; the prediction; delta[2:] as aligned rows)
+    layernorm_fwd -> gemm_nt(+bias, GELU, +residual)                  (`ffeat_norm` — GroupNorm(1, C) on [M, C] rows is a row LayerNorm — and `ffeat_updater`)
+and every row keeps the order (b, n, s) through the loop: nothing is permuted.
+
+fp32 only.  The loop feeds its coordinates back through sin(~970 * flow) (utils.py:110-119: div_term reaches 62 * 1000 / 64) and amplifies rounding by
+about an order of magnitude per iteration; with the reference's own modules, fp32 against fp64 already differs by up to a pixel after four iterations at
+unit-scale `flow_head` weights.  A 16-bit operand mode would start that growth from 2^-9 instead of 2^-24 and is not offered.
+
+The module stays the user's: this class reads its parameters (duck-typed on the attribute names, as teacher_blocks._BlockParams does) and refuses, naming the
+attribute, anything the kernels do not serve.  Off by default (teacher_runner.VGGTTeacherRunner(fused_tracker=True))."""
+import torch
+
+from . import ops
+from ._lib import GdHipError
+
+C_LATENT, MAX_RADIUS, MAX_LEVELS = 128, 4, 8
+
+
+def _exact_gelu(m):
+    return isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none"
+
+
+def level_sizes(H, W, levels):
+    """[(H_l, W_l)] of the pyramid (floor halving, blocks.py:168-176)."""
+    out = [(int(H), int(W))]
+    for _ in range(levels - 1):
+        out.append((out[-1][0] // 2, out[-1][1] // 2))
+    return out
+
+
+def check_levels(H, W, levels, who="FusedTracker"):
+    """A level whose map has a side of 1 (or 0) is refused: there the reference's 2 / max(size - 1, 1) normalisation sends every sample to cell 0,
+    which the integer-window form does not reproduce."""
+    for l, (h, w) in enumerate(level_sizes(H, W, levels)):
+        if h < 2 or w < 2:
+            raise GdHipError(f"{who}: level {l} of a {H} x {W} map is {h} x {w}: a pyramid level with a side below 2 is not served "
+                             f"({levels} levels need sides of at least {2 ** levels})")
+
+
+class TrackState:
+    """What one call carries from iteration to iteration.  coords [B, N, S, 2] (map cells) and track_feats [B, N, S, C] are in the loop's row order;
+    `load` / `coords_bsn` / `feats_bsn` translate from and to the module's [B, S, N, .]."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def load(self, coords_bsn=None, feats_bsn=None):
+        if coords_bsn is not None:
+            self.coords = coords_bsn.float().permute(0, 2, 1, 3).contiguous()
+        if feats_bsn is not None:
+            self.feats = feats_bsn.float().permute(0, 2, 1, 3).contiguous()
+        return self
+
+    @property
+    def coords_bsn(self):
+        return self.coords.permute(0, 2, 1, 3)
+
+    @property
+    def feats_bsn(self):
+        return self.feats.permute(0, 2, 1, 3)
+
+
+class FusedTracker:
+    """FusedTracker(tracker).forward(query_points, fmaps, iters, ...) -> what the module's forward returns.  fp32 only (see the module docstring:
+    a 16-bit mode is not offered).  The parameters are read and packed once, here, on whatever device the module is on (build it after loading the
+    checkpoint); if that is not the device of the feature map handed to `begin` / `forward`, the packed copies are moved there on that call (`_to`).
+    The user's `updateformer` is called as it stands and must itself live on the feature map's device."""
+
+    def __init__(self, tracker, name="tracker"):
+        self.name = name
+
+        def fail(attr, why):
+            raise GdHipError(f"FusedTracker: {name}.{attr}: {why}")
+
+        def need(obj, attr, where=""):
+            if getattr(obj, attr, None) is None:
+                fail(where + attr, "missing")
+            return getattr(obj, attr)
+        f32 = lambda t: t.detach().float().contiguous()
+        C = int(need(tracker, "latent_dim"))
+        if C != C_LATENT:
+            fail("latent_dim", f"{C}: the tracker kernels serve {C_LATENT}")
+        self.C, self.D = C, 3 * C + 4
+        self.radius, self.levels = int(need(tracker, "corr_radius")), int(need(tracker, "corr_levels"))
+        if not 0 <= self.radius <= MAX_RADIUS:
+            fail("corr_radius", f"{self.radius}: gd_corr_sample serves 0 .. {MAX_RADIUS}")
+        if not 1 <= self.levels <= MAX_LEVELS:
+            fail("corr_levels", f"{self.levels}: gd_corr_sample serves 1 .. {MAX_LEVELS}")
+        self.stride, self.max_scale = need(tracker, "stride"), float(need(tracker, "max_scale"))
+        if self.max_scale == 0:
+            fail("max_scale", "0")
+        fn = need(tracker, "fmap_norm")
+        if not (isinstance(fn, torch.nn.LayerNorm) and fn.elementwise_affine and fn.bias is not None and tuple(fn.normalized_shape) == (C,)):
+            fail("fmap_norm", f"not an affine LayerNorm({C})")
+        self.fmap_norm = (f32(fn.weight), f32(fn.bias), float(fn.eps))
+        gn = need(tracker, "ffeat_norm")
+        if not (isinstance(gn, torch.nn.GroupNorm) and gn.affine and gn.num_groups == 1 and gn.num_channels == C):
+            fail("ffeat_norm", f"not an affine GroupNorm(1, {C})")
+        self.ffeat_norm = (f32(gn.weight), f32(gn.bias), float(gn.eps))
+        # corr_mlp: Linear(levels * (2r+1)^2 -> hidden), exact GELU, Linear(hidden -> C); K is padded to the fp32 GEMM's 128-byte K steps
+        mlp = need(tracker, "corr_mlp")
+        fc1, fc2 = need(mlp, "fc1", "corr_mlp."), need(mlp, "fc2", "corr_mlp.")
+        if not _exact_gelu(getattr(mlp, "act", None)):
+            fail("corr_mlp.act", f"{getattr(mlp, 'act', None)}: the GEMM epilogue serves exact (erf) GELU")
+        K = self.levels * (2 * self.radius + 1) ** 2
+        if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear)) or fc1.in_features != K or fc2.in_features != fc1.out_features or \
+                fc2.out_features != C:
+            fail("corr_mlp", f"fc1 / fc2 do not map {K} -> hidden -> {C}")
+        self.kpad = (K + 31) // 32 * 32
+        self._gemm_ok("corr_mlp.fc1", self.kpad, fail)
+        self._gemm_ok("corr_mlp.fc2", fc2.in_features, fail)
+        w1 = torch.zeros(fc1.out_features, self.kpad, dtype=torch.float32, device=fc1.weight.device)
+        w1[:, :K] = fc1.weight.detach().float()
+        self.corr_mlp = (w1, self._bias(fc1), f32(fc2.weight), self._bias(fc2))
+        up = need(tracker, "ffeat_updater")
+        mods = list(up) if isinstance(up, torch.nn.Sequential) else []
+        if len(mods) != 2 or not isinstance(mods[0], torch.nn.Linear) or mods[0].in_features != C or mods[0].out_features != C:
+            fail("ffeat_updater", f"not Sequential(Linear({C}, {C}), GELU)")
+        if not _exact_gelu(mods[1]):
+            fail("ffeat_updater[1]", f"{mods[1]}: the GEMM epilogue serves exact (erf) GELU")
+        self._gemm_ok("ffeat_updater[0]", C, fail)
+        self.ffeat_updater = (f32(mods[0].weight), self._bias(mods[0]))
+        self.updateformer = need(tracker, "updateformer")
+        qrt = need(tracker, "query_ref_token")
+        if tuple(qrt.shape) != (1, 2, self.D):
+            fail("query_ref_token", f"{tuple(qrt.shape)}, not (1, 2, {self.D})")
+        self.qrt = f32(qrt).reshape(2, self.D)
+        self.predict_conf = bool(getattr(tracker, "predict_conf", False))
+        heads = [("vis_predictor", need(tracker, "vis_predictor"))]
+        if self.predict_conf:
+            if getattr(tracker, "conf_predictor", None) is None:
+                fail("conf_predictor", "missing while predict_conf is set")
+            heads.append(("conf_predictor", tracker.conf_predictor))
+        # the one-output predictors share ONE GEMM: their weights are rows 0 (vis) and 1 (conf) of an [8, C] matrix, the other rows zero
+        wp = torch.zeros(8, C, dtype=torch.float32, device=self.qrt.device)
+        bp = torch.zeros(8, dtype=torch.float32, device=self.qrt.device)
+        for i, (attr, m) in enumerate(heads):
+            lin = m[0] if isinstance(m, torch.nn.Sequential) and len(m) == 1 else m
+            if not isinstance(lin, torch.nn.Linear) or lin.in_features != C or lin.out_features != 1:
+                fail(attr, f"not a Linear({C}, 1) (alone or as the only entry of a Sequential)")
+            wp[i] = lin.weight.detach().float()[0]
+            if lin.bias is not None:
+                bp[i] = lin.bias.detach().float()[0]
+        self.predictors = (wp, bp)
+        self._omega = {}
+
+    _TENSORS = ("fmap_norm", "ffeat_norm", "corr_mlp", "ffeat_updater", "predictors")
+
+    def _to(self, device):
+        """The packed parameters follow the feature map's device: a tracker read while the teacher was still on the host is moved on its first call."""
+        if self.qrt.device != device:
+            self.qrt = self.qrt.to(device)
+            for n in self._TENSORS:
+                setattr(self, n, tuple(v.to(device) if torch.is_tensor(v) else v for v in getattr(self, n)))
+
+    @staticmethod
+    def _bias(lin):
+        return lin.bias.detach().float().contiguous() if lin.bias is not None else torch.zeros(lin.out_features, dtype=torch.float32, device=lin.weight.device)
+
+    @staticmethod
+    def _gemm_ok(attr, K, fail):
+        """gd_gemm_nt takes fp32 operands whose K and row strides are multiples of 16 bytes: refused here, at construction, not in the loop."""
+        if K % 4:
+            fail(attr, f"K = {K}: the fp32 GEMM takes K in multiples of 4")
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    def _channel_last(self, fmaps, fmaps_cl, pitch):
+        """-> (map [B*S, H, pitch, C] contiguous fp32, B, S, H, W, pitch).  fmaps: NCHW [B, S, C, H, W].  fmaps_cl: [B, S, H, W, C], either contiguous
+        or the data columns of a pitched buffer (strides (S*H*pitch*C, H*pitch*C, pitch*C, C, 1), e.g. FusedDPTHead(..., channel_last=True))."""
+        C = self.C
+        if (fmaps is None) == (fmaps_cl is None):
+            raise GdHipError("FusedTracker: give fmaps (NCHW) or fmaps_cl (channel-last), not both")
+        if fmaps is not None:
+            if fmaps.dim() != 5 or fmaps.shape[2] != C or not fmaps.is_cuda:
+                raise GdHipError(f"FusedTracker: fmaps {tuple(fmaps.shape)} on {fmaps.device} is not [B, S, {C}, H, W] on the GPU")
+            B, S, _, H, W = fmaps.shape
+            return fmaps.float().permute(0, 1, 3, 4, 2).contiguous().view(B * S, H, W, C), B, S, H, W, W
+        t = fmaps_cl
+        if t.dim() != 5 or t.shape[4] != C or not t.is_cuda or t.dtype != torch.float32:
+            raise GdHipError(f"FusedTracker: fmaps_cl {tuple(t.shape)} {t.dtype} on {t.device} is not fp32 [B, S, H, W, {C}] on the GPU")
+        B, S, H, W, _ = t.shape
+        p = self.pitch_of(t, pitch)
+        if p == W:
+            return torch.as_strided(t, (B * S, H, W, C), (H * W * C, W * C, C, 1)), B, S, H, W, W
+        try:
+            return torch.as_strided(t, (B * S, H, p, C), (H * p * C, p * C, C, 1)), B, S, H, W, p
+        except RuntimeError as e:
+            raise GdHipError(f"FusedTracker: fmaps_cl does not sit in a buffer of whole pitched rows (pitch {p}): {e}")
+
+    @staticmethod
+    def pitch_of(t, pitch=None):
+        """The pitch (cells per map row in memory) of a channel-last map t [B, S, H, W, C]: `pitch` when given, else read off the row stride.  Raises unless
+        t's strides are those of [B, S, H, pitch, C] rows; the stride of a dimension of size 1 is arbitrary and is not compared."""
+        B, S, H, W, C = t.shape
+        p = int(pitch) if pitch is not None else (t.stride(2) // C if H > 1 else W)
+        want = (S * H * p * C, H * p * C, p * C, C, 1)
+        if p < W or any(n > 1 and st != w for n, st, w in zip(t.shape, t.stride(), want)):
+            raise GdHipError(f"FusedTracker: fmaps_cl strides {tuple(t.stride())} are not those of [B, S, H, pitch = {p}, {C}] rows")
+        return p
+
+    @torch.no_grad()
+    def begin(self, query_points, fmaps=None, down_ratio=1, *, fmaps_cl=None, pitch=None):
+        """-> the TrackState before the first iteration (base_track_predictor.py:88-118)."""
+        fm, B, S, H, W, p = self._channel_last(fmaps, fmaps_cl, pitch)
+        self._to(fm.device)
+        if query_points.dim() != 3 or query_points.shape[0] != B or query_points.shape[2] != 2:
+            raise GdHipError(f"FusedTracker: query_points {tuple(query_points.shape)} is not [B = {B}, N, 2]")
+        check_levels(H, W, self.levels)
+        C, N = self.C, query_points.shape[1]
+        q = query_points.to(fm.device, torch.float32)
+        if down_ratio > 1:
+            q = q / float(down_ratio)
+        q = (q / float(self.stride)).contiguous()
+        g, b, eps = self.fmap_norm
+        fm = ops.layernorm_fwd(fm.view(B * S * H * p, C), g, b, eps, save_stats=False)[0].view(B * S, H, p, C)       # separator rows: finite, never read
+        pyramid = ops.corr_pyramid(fm, W, self.levels)
+        qfeat = ops.points_bilinear(fm, W, q, frame_step=S)
+        key = str(fm.device)
+        if key not in self._omega:
+            self._omega[key] = ops.track_pos_omega(self.D, fm.device)
+        return TrackState(B=B, S=S, N=N, H=H, W=W, pyramid=pyramid, query_feat=qfeat,
+                          coords=q[:, :, None, :].expand(B, N, S, 2).contiguous(), feats=qfeat[:, :, None, :].expand(B, N, S, C).contiguous(),
+                          pos=ops.track_pos_embed(q.view(B * N, 2), H, W, self.D, self._omega[key]),
+                          mul1=float(self.stride), mul2=float(down_ratio) if down_ratio > 1 else 1.0)
+
+    @torch.no_grad()
+    def step(self, st):
+        """One iteration (base_track_predictor.py:123-192): updates st.coords / st.feats, -> the predicted coordinates [B, S, N, 2] at image scale."""
+        B, S, N, C = st.B, st.S, st.N, self.C
+        M = B * N * S
+        corr = ops.corr_sample(st.pyramid, st.feats, st.coords, self.radius, ld=self.kpad)
+        st.corr = corr
+        w1, b1, w2, b2 = self.corr_mlp
+        c = ops.gemm_nt(ops.gemm_nt(corr.view(M, self.kpad), w1, bias=b1, act=1), w2, bias=b2)
+        x = ops.track_assemble(st.coords, c.view(B, S, N, C), st.feats, st.pos, self.qrt, self.max_scale)
+        delta = self.updateformer(x)
+        delta = delta[0] if isinstance(delta, (tuple, list)) else delta
+        if tuple(delta.shape) != (B, N, S, C + 2):
+            raise GdHipError(f"FusedTracker: {self.name}.updateformer returned {tuple(delta.shape)}, not {(B, N, S, C + 2)}")
+        pred, dfeat = ops.track_update(delta.float(), st.coords, st.mul1, st.mul2)
+        g, b, eps = self.ffeat_norm
+        y = ops.layernorm_fwd(dfeat, g, b, eps, save_stats=False)[0]
+        wu, bu = self.ffeat_updater
+        st.feats = ops.gemm_nt(y, wu, bias=bu, act=1, residual=st.feats.view(M, C)).view(B, N, S, C)
+        return pred
+
+    @torch.no_grad()
+    def finish(self, st, apply_sigmoid=True):
+        """-> (vis [B, S, N], conf [B, S, N] or None) (base_track_predictor.py:194-204)."""
+        B, S, N, C = st.B, st.S, st.N, self.C
+        o = ops.gemm_nt(st.feats.view(B * N * S, C), self.predictors[0], bias=self.predictors[1]).view(B, N, S, 8)
+        vis = o[..., 0].permute(0, 2, 1)
+        conf = o[..., 1].permute(0, 2, 1) if self.predict_conf else None
+        if apply_sigmoid:
+            vis, conf = torch.sigmoid(vis), (torch.sigmoid(conf) if conf is not None else None)
+        return vis, conf
+
+    @torch.no_grad()
+    def forward(self, query_points, fmaps=None, iters=6, return_feat=False, down_ratio=1, apply_sigmoid=True, *, fmaps_cl=None, pitch=None):
+        """Same arguments and result as the module's forward: ([iters x coords [B, S, N, 2] at image scale], vis, conf), or with return_feat
+        (coords, vis, track_feats [B, S, N, C], query_track_feat [B, N, C], conf).  fmaps_cl / pitch: the channel-last map (see _channel_last)."""
+        st = self.begin(query_points, fmaps, down_ratio, fmaps_cl=fmaps_cl, pitch=pitch)
+        preds = [self.step(st) for _ in range(iters)]
+        vis, conf = self.finish(st, apply_sigmoid)
+        if return_feat:
+            return preds, vis, st.feats_bsn, st.query_feat, conf
+        return preds, vis, conf
+
+    __call__ = forward

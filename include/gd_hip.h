@@ -595,6 +595,41 @@ int gd_color_jitter_u8(const unsigned char* src, unsigned char* dst, int n, int 
 int gd_gaussian_blur_u8(const unsigned char* src, float* tmp, unsigned char* dst, int n, int H, int W, const int* ksize,
                         void* stream);
 
+/* The VGGT teacher's tracker tail (vggt/heads/track_modules/base_track_predictor.py:82-209) without the correlation volume.  Every map is
+ * channel-last [F = B * S, H, pitch, C] fp32 with C = 128 (anything else is refused); columns x >= W of a pitched row are never read.  All
+ * arguments are checked before any HIP call.
+ * gd_avgpool2_cl: the next pyramid level, dst [F, H / 2, pitch_out, C] = the 2 x 2 mean at stride 2 of src [F, H, pitch_in, C]; an odd last row
+ *   or column is dropped, columns x >= W / 2 of dst are written as zeros.  Replaces blocks.py:168-176 (F.avg_pool2d(kernel_size=2, stride=2),
+ *   each level pooled from the previous one).
+ * gd_corr_sample: CorrBlock.corr_sample (blocks.py:186-246: matmul of the targets with every cell, / sqrt(C), grid_sample of the (2r+1)^2
+ *   window with align_corners=True and zero padding) for all levels at once.  maps: HOST array of `levels` device pointers; dims: HOST array
+ *   [levels][3] = {H, W, pitch}; targets [B, N, S, C] and coords [B, N, S, 2] (level-0 cells); out [B * S, N, ld], ld >= levels * (2r+1)^2.
+ *   For every (frame, point, level): d(cell) = <target, map[cell]> / sqrt(C) on the (2r+2)^2 integer cells around coords / 2^level (0
+ *   outside the map), then out[level * (2r+1)^2 + a * (2r+1) + b] = the bilinear blend at (x + a - r, y + b - r) — the reference's window
+ *   order, whose FIRST axis moves x (blocks.py:181-184) — all with the one fractional part of (x, y).  Columns from levels * (2r+1)^2 up
+ *   to ld are written as zeros.  radius <= 4, levels <= 8; a level with a side of 1 is refused (the reference's 2 / max(size - 1, 1)
+ *   normalisation sends every sample to cell 0 there); a non-finite or |.| >= 1e9 coordinate gives zeros.
+ * gd_points_bilinear: sample_features4d (utils.py:196-226; base_track_predictor.py:111) — out [B, N, C] = the bilinear sample
+ *   (align_corners=True, coordinates clamped to the map) of frame b * frame_step of map [., H, pitch, C] at points [B, N, 2] (x, y).
+ * gd_track_pos_embed: get_2d_sincos_pos_embed(D, (H, W)) sampled at M points (utils.py:18-90, base_track_predictor.py:149-150), out [M, D]:
+ *   channels [0, D/2) = [sin | cos](x w_k), [D/2, D) the same of y, each the 1-D blend of the two neighbouring columns (border clamp);
+ *   omega [D / 4] = 10000^(-k / (D / 4)) as floats.  The [1, D, H, W] table is never built.
+ * gd_track_assemble: the update transformer's input (base_track_predictor.py:135-160), rows (b, n, s): x [B * N * S, 3C + 4] =
+ *   [get_2d_embedding(flow, C / 2) (C) | flow / max_scale (2) | flow / max_scale (2) | corr [B, S, N, C] (corr_mlp's output rows) |
+ *   feats [B, N, S, C]] + pos [B * N, 3C + 4] + ref_token [2, 3C + 4] (row 0 for s = 0, row 1 otherwise); flow = coords[b, n, s] - coords[b, n, 0].
+ * gd_track_update: base_track_predictor.py:169-192 — coords [B, N, S, 2] += delta[:, :2] for s > 0 (frame 0 stays the query), pred
+ *   [B, S, N, 2] = (coords * mul1) * mul2, dfeat [B * N * S, C] = delta[:, 2:] (delta [B * N * S, ldd >= C + 2]). */
+int gd_avgpool2_cl(const float* src, float* dst, int frames, int H, int W, int pitch_in, int pitch_out, int C, void* stream);
+int gd_corr_sample(const float* const* maps, const int* dims, int levels, int radius, const float* targets, const float* coords, int B, int S,
+                   int N, int C, float* out, long ld, void* stream);
+int gd_points_bilinear(const float* map, const float* points, float* out, int B, int N, int H, int W, int pitch, int C, long frame_step,
+                       void* stream);
+int gd_track_pos_embed(const float* points, const float* omega, float* out, long M, int H, int W, int D, void* stream);
+int gd_track_assemble(const float* coords, const float* corr, const float* feats, const float* pos, const float* ref_token, float* x, int B,
+                      int S, int N, int C, float max_scale, void* stream);
+int gd_track_update(const float* delta, long ldd, float* coords, float* pred, float* dfeat, int B, int S, int N, int C, float mul1, float mul2,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -30,6 +30,12 @@
    (f32 and bf16 operands) against the torch module of tests/mast3r_head_layout.py (f32, and under bf16 autocast), measured as section 5 is.
    "mast3r_heads_share" (--sections mast3r_heads_share): a MASt3R-shaped random-weight teacher (the transformer of section 4 with fused_blocks in
    bf16, a linear patch embedding, two such heads): `targets()` of one pair and the two heads alone, on the modules and with fused_heads (f32, bf16).
+7. "vggt_tracker" (--sections tracker): the tracker tail at teacher size — a 259 x 259 x 128 feature map, S = 2 frames, N = 300 points, 7 pyramid levels, radius 4,
+   4 iterations, hidden size 384, depth 6, random weights: the torch module of tests/tracker_layout.py as it stands (the position table rebuilt on the host in
+   every iteration, as the reference does), the same with the table cached on the device, and teacher_tracker.FusedTracker (NCHW and channel-last input);
+   gd_corr_sample alone with the bytes per second of the in-map window cells it gathers; the update transformer's share of the fused time.
+   "vggt_tracker_share_of_targets" (--sections tracker_share): the teacher of heads_share with a real tracker behind the 128-feature head, fused_blocks
+   and fused_heads on: `targets()` and the tracker call alone with fused_tracker off and on.
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -104,11 +110,15 @@ def main():
         mast3r_head_section(res, a, dev)
     if "mast3r_heads_share" in sections:
         mast3r_share_section(res, a, dev)
+    if "tracker" in sections:
+        tracker_section(res, a, dev)
+    if "tracker_share" in sections:
+        tracker_share_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
            "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
-           "mast3r_heads_share": ["mast3r_heads_share"]}
+           "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -208,6 +218,101 @@ def dpt_share_section(res, a, dev):
         out[tag]["heads_share_of_targets"] = round(out[tag]["three_heads"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
         del r
     res["vggt_dpt_heads_share_of_targets"] = out
+
+
+TRACKER = dict(H=259, W=259, S=2, N=300, levels=7, radius=4, iters=4, hidden_size=384, depth=6)
+
+
+def teacher_size_tracker(dev, **kw):
+    import tracker_layout as TL
+    with torch.device(dev):
+        return TL.TrackerLayout(stride=2, corr_levels=TRACKER["levels"], corr_radius=TRACKER["radius"], hidden_size=TRACKER["hidden_size"],
+                                depth=TRACKER["depth"], **kw).eval()
+
+
+def tracker_section(res, a, dev):
+    from gd_amd.teacher_tracker import FusedTracker
+    t = TRACKER
+    H, W, S, N, iters = t["H"], t["W"], t["S"], t["N"], t["iters"]
+    trk = teacher_size_tracker(dev)
+    cached = teacher_size_tracker(dev, cache_pos_embed=True)
+    cached.load_state_dict(trk.state_dict())
+    fused = FusedTracker(trk)
+    fmaps = torch.randn(1, S, 128, H, W, device=dev)
+    cl = fmaps.permute(0, 1, 3, 4, 2).contiguous()
+    q = torch.rand(1, N, 2, device=dev) * torch.tensor([2.0 * (W - 1), 2.0 * (H - 1)], device=dev)
+
+    def module_run(m):
+        with torch.no_grad():
+            return m(q, fmaps, iters=iters)
+    out = dict(t, updateformer="the torch module in every path", dtype="float32")
+    want, got = module_run(cached)[0][-1], fused(q, fmaps, iters=iters)[0][-1]
+    out["fused_vs_module_final_coords_max_abs_px"] = float((want - got).abs().max())       # random unit-scale weights: the loop amplifies rounding
+    # the host-built table costs seconds per call: fewer windows for that path
+    out["module_host_table"] = timed(lambda: module_run(trk), 1, min(a.iters, 3))
+    for name, fn in (("module_cached_table", lambda: module_run(cached)), ("fused", lambda: fused(q, fmaps, iters=iters)),
+                     ("fused_channel_last", lambda: fused(q, iters=iters, fmaps_cl=cl))):
+        out[name] = timed(fn, a.warm, a.iters)
+    st = fused.begin(q, fmaps)
+    out["corr_sample"] = timed(lambda: ops.corr_sample(st.pyramid, st.feats, st.coords, fused.radius, ld=fused.kpad), a.warm, a.iters, reps=20)
+    cells = 0                                   # the in-map cells of every (2r+2)^2 window: what the kernel's dot products read (512 B each)
+    for l, (_m, h, w, _p) in enumerate(st.pyramid):
+        c0 = (st.coords / 2 ** l).floor().long() - fused.radius
+        k = torch.arange(2 * fused.radius + 2, device=dev)
+        nx = ((c0[..., 0:1] + k >= 0) & (c0[..., 0:1] + k < w)).sum(-1)
+        ny = ((c0[..., 1:2] + k >= 0) & (c0[..., 1:2] + k < h)).sum(-1)
+        cells += int((nx * ny).sum())
+    out["corr_sample"]["gathered_MB"] = round(cells * 512 / 1e6, 1)
+    out["corr_sample"]["gathered_GBps"] = round(cells * 512 / 1e9 / (out["corr_sample"]["median_ms"] * 1e-3), 1)
+    x = torch.randn(1, N, S, fused.D, device=dev)
+
+    def former():
+        with torch.no_grad():
+            trk.updateformer(x)
+    out["updateformer_one_call"] = timed(former, a.warm, a.iters)
+    out["updateformer_share_of_fused"] = round(iters * out["updateformer_one_call"]["median_ms"] / out["fused"]["median_ms"], 3)
+    res["vggt_tracker"] = out
+
+
+def tracker_share_section(res, a, dev):
+    import dpt_layout as DL
+    import tracker_layout as TL
+    C, S = a.width, 2
+    idx = [a.depth // 6, a.depth // 2 - 1, 3 * a.depth // 4 - 1, a.depth - 1]
+    with torch.device(dev):
+        agg = AggregatorLayout(img_size=a.img, patch_size=14, embed_dim=C, depth=a.depth, num_heads=C // 64, num_register_tokens=4,
+                               attn_indices=[a.depth // 2, a.depth - 1], temperature=0.8).eval()
+        head = lambda **kw: DL.DPTLayout(**dict(dict(VGGT_HEAD, dim_in=2 * C), intermediate_layer_idx=idx, **kw)).eval()
+        track = TL.TrackHeadLayout(2 * C, levels=TRACKER["levels"], iters=TRACKER["iters"])
+        track.feature_extractor = head(features=128, feature_only=True, down_ratio=2)
+        depth_head, point_head = head(output_dim=2, activation="exp"), head(output_dim=4, activation="inv_log")
+    track.tracker = teacher_size_tracker(dev)
+    rope = T.DeviceRope2D()
+    agg.rope = rope
+    for b in list(agg.frame_blocks) + list(agg.global_blocks):
+        b.attn.rope = rope
+        torch.nn.init.constant_(b.ls1.gamma, 0.2)
+        torch.nn.init.constant_(b.ls2.gamma, 0.2)
+    teacher = type("Teacher", (), {"aggregator": agg, "depth_head": depth_head, "point_head": point_head,
+                                   "track_head": track.eval(), "camera_head": lambda self, toks: [torch.zeros(1, 2, 9, device=dev)]})()
+    img = torch.rand(1, S, 3, (a.img // 14) * 14, (a.img // 14) * 14, device=dev)
+    out = dict(TRACKER, width=C, depth=a.depth, aggregator="fused_blocks bf16", heads="fused_heads f32")
+    for tag, on in (("module_tracker", False), ("fused_tracker", True)):
+        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=on)
+        toks, ps, _ = r.aggregate(img)
+        fm, pitch = r.heads["track_head.feature_extractor"](toks, img, ps, channel_last=True)
+        nchw = fm.permute(0, 1, 4, 2, 3)
+        q = torch.rand(1, TRACKER["N"], 2, device=dev) * (img.shape[-1] - 1)
+
+        def tracker_run():
+            with torch.no_grad():
+                return r.tracker(q, iters=track.iters, fmaps_cl=fm, pitch=pitch) if on else track.tracker(query_points=q, fmaps=nchw, iters=track.iters)
+        got = r.targets(img)
+        out[tag] = {"tracker": timed(tracker_run, 1, min(a.iters, 3)), "targets": timed(lambda: r.targets(img), 1, min(a.iters, 3)),
+                    "targets_returned_none": got is None, "keypoints": 0 if got is None else int(got["kp_1"].shape[0])}
+        out[tag]["tracker_share_of_targets"] = round(out[tag]["tracker"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
+        del r
+    res["vggt_tracker_share_of_targets"] = out
 
 
 MAST3R_HEAD = dict(enc_dim=1024, dec_dim=768, feature_dim=256, last_dim=128, local_feat_dim=24, two_confs=True)
