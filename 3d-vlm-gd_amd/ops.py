@@ -502,6 +502,28 @@ def cross_attention_fwd(q, kv, B, Nq, Nk, H, want_lse=False, x3=False):
     return o, lse
 
 
+def attention_small_fwd(q, k, v, G0, G1, Nq, Nk, H, scale=None, out=None):
+    """q [G0, G1, Nq, H*hd], k, v [G0, G1, Nk, H*hd]: fp32 strided 4-D views (last dim contiguous; every other stride, read off the tensor, a
+    multiple of 4 elements — column blocks of one packed tensor and tokens that are not neighbours in memory are fine) -> o [G0, G1, Nq, H*hd]
+    = softmax(scale q k^T) v per (g0, g1, head), contiguous unless `out=` (a view of the same kind, overlapping no input) is given
+    (gd_attention_small_fwd: exact fp32, hd a multiple of 4 up to 64, short sequences; scale defaults to hd^-0.5)."""
+    for t, n, what in ((q, Nq, "q"), (k, Nk, "k"), (v, Nk, "v")) + (((out, Nq, "out"),) if out is not None else ()):
+        _req(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and tuple(t.shape[:3]) == (G0, G1, n) and t.shape[3] == q.shape[3] and
+             t.stride(3) == 1, f"attention_small_fwd: {what} must be a CUDA fp32 view [{G0}, {G1}, {n}, {q.shape[3]}] with a contiguous last dim, "
+             f"got {tuple(t.shape)} {t.dtype} strides {tuple(t.stride())}")
+    W = q.shape[3]
+    _req(H >= 1 and W % H == 0, f"attention_small_fwd: width {W} is not a multiple of H = {H}")
+    hd = W // H
+    o = torch.empty(G0, G1, Nq, W, dtype=torch.float32, device=q.device) if out is None else out
+    # the stride of a dimension of size 1 is arbitrary in torch and addresses nothing: 0 (W for the row stride) goes down instead
+    st = lambda t: tuple(t.stride(d) if t.shape[d] > 1 else 0 for d in (0, 1))
+    ld = lambda t: t.stride(2) if t.shape[2] > 1 else W
+    rc = lib().gd_attention_small_fwd(ptr(q), ptr(k), ptr(v), ptr(o), G0, G1, Nq, Nk, H, hd, ld(q), ld(k), ld(v), ld(o),
+                                      *st(q), *st(k), *st(v), *st(o), float(hd ** -0.5 if scale is None else scale), stream())
+    check(rc, "gd_attention_small_fwd")
+    return o
+
+
 def attention_bwd(qkv, o, dout, lse, B, N, H, vfirst=False, need_dk=True, x3=False):
     """-> dqkv [B*N, 3*H*64] (same dtype as qkv), column blocks (dq, dk, dv) — or (dq, dv, dk) with vfirst.  need_dk=False: the dK
     columns are left unwritten (bf16: the dK/dV kernel then runs its dV half only)."""
@@ -1727,7 +1749,13 @@ def track_update(delta, coords, mul1=1.0, mul2=1.0):
     B, N, S, C2 = delta.shape
     C = C2 - 2
     _f32c(coords, (B, N, S, 2), "track_update: coords")
-    d = delta.reshape(B * N * S, C2) if delta.is_contiguous() else delta.contiguous().view(B * N * S, C2)
+    ldd = delta.stride(2)
+    if delta.is_contiguous():
+        d = delta.reshape(B * N * S, C2)
+    elif ldd >= C2 and all(n == 1 or s == w for n, s, w in zip(delta.shape, delta.stride(), (N * S * ldd, S * ldd, ldd, 1))):
+        d = torch.as_strided(delta, (B * N * S, C2), (ldd, 1))          # the columns of wider rows (e.g. a GEMM's padded output): read in place
+    else:
+        d = delta.contiguous().view(B * N * S, C2)
     _req(d.is_cuda and d.dtype == torch.float32, "track_update: delta must be a CUDA fp32 tensor")
     pred = torch.empty(B, S, N, 2, dtype=torch.float32, device=d.device)
     dfeat = torch.empty(B * N * S, C, dtype=torch.float32, device=d.device)

@@ -103,7 +103,9 @@ class VGGTTeacherRunner:
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
     def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32,
-                 fused_tracker=False):
+                 fused_updateformer=False, fused_tracker=False):
+        if fused_updateformer and not fused_tracker:
+            raise GdHipError("VGGTTeacherRunner: fused_updateformer=True needs fused_tracker=True (the fused update transformer runs inside FusedTracker's loop)")
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
         agg = vggt.aggregator
         per = getattr(agg, "aa_block_size", 1)
@@ -122,12 +124,13 @@ class VGGTTeacherRunner:
             self.heads = {n: FusedDPTHead(h, dtype=heads_dtype, name=n) for n, h in (("depth_head", vggt.depth_head), ("point_head", vggt.point_head),
                                                                                       ("track_head.feature_extractor", vggt.track_head.feature_extractor))}
         # fused_tracker: the tracker's correlation pyramid, window sampling, position embedding, glue and small MLPs run on the HIP kernels
-        # (teacher_tracker.FusedTracker, fp32; the update transformer stays the user's module).  Independent of fused_blocks and fused_heads; a tracker the
+        # (teacher_tracker.FusedTracker, fp32; the update transformer stays the user's module unless fused_updateformer, off by default, hands it to
+        # teacher_tracker.FusedUpdateFormer; pass both by keyword, fused_tracker stays the last one).  Independent of fused_blocks and fused_heads; a tracker the
         # class refuses raises here, not in targets().
         self.tracker = None
         if fused_tracker:
             from .teacher_tracker import FusedTracker
-            self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker")
+            self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker", fused_updateformer=fused_updateformer)
 
     def _block_inputs(self, rgb_vggt):
         """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the

@@ -12,7 +12,7 @@ What the reference does in every iteration and this class does not:
 One iteration (`step`) is
     corr_sample -> gemm_nt(+bias, GELU) -> gemm_nt(+bias)            (the window samples, `corr_mlp`)
     track_assemble                                                    (flow embedding | flow / max_scale | corr | track_feats, + position + query token)
-    updateformer                                                      (the USER'S module, called as it stands)
+    updateformer                                                      (the USER'S module, called as it stands; FusedUpdateFormer with fused_updateformer=True)
     track_update                                                      (coords += delta[:2], frame 0 pinned; the prediction; delta[2:] as aligned rows)
     layernorm_fwd -> gemm_nt(+bias, GELU, +residual)                  (`ffeat_norm` — GroupNorm(1, C) on [M, C] rows is a row LayerNorm — and `ffeat_updater`)
 and every row keeps the order (b, n, s) through the loop: nothing is permuted.
@@ -52,6 +52,233 @@ def check_levels(H, W, levels, who="FusedTracker"):
                              f"({levels} levels need sides of at least {2 ** levels})")
 
 
+def _ln_params(m, attr, fail, width=None):
+    if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and m.weight is not None and m.bias is not None) or \
+            (width is not None and tuple(m.normalized_shape) != (width,)):
+        fail(attr, f"not an affine LayerNorm{'' if width is None else f'({width})'} with a bias")
+    return (m.weight.detach().float().contiguous(), m.bias.detach().float().contiguous(), float(m.eps))
+
+
+def _lin_bias(b, n, like):
+    return b.detach().float().contiguous() if b is not None else torch.zeros(n, dtype=torch.float32, device=like.device)
+
+
+class FusedUpdateFormer:
+    """FusedUpdateFormer(updateformer)(x [B, N, S, 3C + 4]) -> (delta [B, N, S, C + 2], None): the tracker's update transformer
+    (vggt/heads/track_modules/blocks.py:19-144 EfficientUpdateFormer on modules.py:147-218 AttnBlock / CrossAttnBlock) on gd_layernorm_fwd, gd_gemm_nt
+    and gd_attention_small_fwd, fp32 only.
+
+    There is ONE token buffer [B, N + nv, S, D], rows in the order (b, n, s) the tracker loop keeps, the nv virtual tracks behind the points; no
+    token tensor is permuted, concatenated or repeated per block, and the virtual rows are written once per call.
+      * a time block takes every row: its sequences are S consecutive rows (G0 = B (N + nv), G1 = 1);
+      * the space stage of frame (b, s) addresses tokens S rows apart (G0 = 1 per batch entry, G1 = S): `virtual2point` (q = virtual rows, k | v = ONE
+        GEMM of norm_context(points) on in_proj_weight[D:]), `virtual` (self-attention on the virtual rows), `point2virtual`; the three write back into
+        the same buffer, so the next time block reads it as it is.
+    A sequence layout is (G0, G1, L, r0, r1, rl): token i of sequence (g0, g1) is row g0 * r0 + g1 * r1 + i * rl of the rows handed over.
+
+    The teacher's block REPLACES x by norm1(x) (modules.py:174-183): the attention's residual is the normed x, not the block input; the same in the
+    cross block.  The blocks whose point rows are the last ones written add them onto the saved input tokens (the GEMM's accumulate), so
+    `tokens[:, :N] + init_tokens` costs no pass of its own; a last time block without a space stage runs on the point rows alone.
+
+    Read once, duck-typed on the attribute names; what the kernels do not serve is refused here, naming the attribute."""
+
+    def __init__(self, former, name="updateformer"):
+        self.name = name
+
+        def fail(attr, why):
+            raise GdHipError(f"FusedUpdateFormer: {name}.{attr}: {why}")
+
+        def need(obj, attr, where=""):
+            if getattr(obj, attr, None) is None:
+                fail(where + attr, "missing")
+            return getattr(obj, attr)
+        f32 = lambda t: t.detach().float().contiguous()
+        it, fh = need(former, "input_transform"), need(former, "flow_head")
+        if not isinstance(it, torch.nn.Linear) or not isinstance(fh, torch.nn.Linear) or fh.in_features != it.out_features:
+            fail("input_transform / flow_head", "not Linear(input -> hidden) and Linear(hidden -> output)")
+        self.Din, self.D, self.Dout = it.in_features, it.out_features, fh.out_features
+        D = self.D
+        for attr, K in (("input_transform", self.Din), ("flow_head", D)):
+            if K % 4:
+                fail(attr, f"K = {K}: the fp32 GEMM takes K in multiples of 4")
+        self.input_norm = _ln_params(need(former, "input_norm"), "input_norm", fail, self.Din)
+        self.output_norm = _ln_params(need(former, "output_norm"), "output_norm", fail, D)
+        self.input_transform = (f32(it.weight), _lin_bias(it.bias, D, it.weight))
+        # flow_head's rows are padded to a multiple of 4 with zeros: the [M, ld] result is handed on as its first Dout columns, without a copy
+        self.ldo = (self.Dout + 3) // 4 * 4
+        wf = torch.zeros(self.ldo, D, dtype=torch.float32, device=fh.weight.device)
+        wf[:self.Dout] = fh.weight.detach().float()
+        bf = torch.zeros(self.ldo, dtype=torch.float32, device=fh.weight.device)
+        if fh.bias is not None:
+            bf[:self.Dout] = fh.bias.detach().float()
+        self.flow_head = (wf, bf)
+        time_blocks = list(need(former, "time_blocks"))
+        vt = getattr(former, "virual_tracks", None)                  # (the reference's spelling)
+        self.nv = int(need(former, "num_virtual_tracks")) if vt is not None else 0
+        if self.nv:
+            if tuple(vt.shape) != (1, self.nv, 1, D):
+                fail("virual_tracks", f"{tuple(vt.shape)}, not (1, {self.nv}, 1, {D})")
+            self.virtual = f32(vt).reshape(self.nv, 1, D)
+            sv, p2v, v2p = (list(need(former, a)) for a in ("space_virtual_blocks", "space_point2virtual_blocks", "space_virtual2point_blocks"))
+            nt, ns = len(time_blocks), len(sv)
+            # blocks.py:122: a space stage after time block i when i % (nt // ns) == 0, taking space blocks 0, 1, ... in turn
+            if ns < 1 or nt < ns or len(p2v) != ns or len(v2p) != ns:
+                fail("space_virtual_blocks", f"{ns} space blocks (point2virtual {len(p2v)}, virtual2point {len(v2p)}) for {nt} time blocks")
+            self.every = nt // ns
+            stages = (nt + self.every - 1) // self.every
+            if stages > ns:
+                fail("space_virtual_blocks", f"time depth {nt} / space depth {ns}: the loop (a stage every {self.every} blocks) would index space block "
+                                             f"{stages - 1} of {ns}")
+        else:
+            self.virtual, self.every, sv, p2v, v2p = None, 1, [], [], []
+        if not time_blocks:
+            fail("time_blocks", "empty")
+        self.time_blocks = [self._block(b, f"time_blocks[{i}]", False, fail, need) for i, b in enumerate(time_blocks)]
+        self.space_virtual_blocks = [self._block(b, f"space_virtual_blocks[{i}]", False, fail, need) for i, b in enumerate(sv)]
+        self.space_point2virtual_blocks = [self._block(b, f"space_point2virtual_blocks[{i}]", True, fail, need) for i, b in enumerate(p2v)]
+        self.space_virtual2point_blocks = [self._block(b, f"space_virtual2point_blocks[{i}]", True, fail, need) for i, b in enumerate(v2p)]
+        self.launches = 0
+
+    def _block(self, blk, where, cross, fail, need):
+        D = self.D
+        f32 = lambda t: t.detach().float().contiguous()
+        aname = where + (".cross_attn" if cross else ".attn")
+        at = need(blk, "cross_attn" if cross else "attn", where + ".")
+        if not isinstance(at, torch.nn.MultiheadAttention):
+            fail(aname, f"{type(at).__name__}: not a torch.nn.MultiheadAttention")
+        if not at.batch_first:
+            fail(aname + ".batch_first", "False")
+        if not at._qkv_same_embed_dim or at.in_proj_weight is None:
+            fail(aname + "._qkv_same_embed_dim", "False: separate q / k / v projection widths are not served")
+        if at.dropout != 0:
+            fail(aname + ".dropout", f"{at.dropout}: the kernel has no dropout")
+        if at.bias_k is not None or at.bias_v is not None:
+            fail(aname + ".bias_k", "set: no appended bias rows")
+        if at.add_zero_attn:
+            fail(aname + ".add_zero_attn", "True")
+        if at.embed_dim != D:
+            fail(aname + ".embed_dim", f"{at.embed_dim}, not the hidden size {D}")
+        H = int(at.num_heads)
+        if H < 1 or D % H:
+            fail(aname + ".num_heads", f"{H} does not divide embed_dim {D}")
+        hd = D // H
+        if hd % 4 or not 4 <= hd <= 64:
+            fail(aname + ".num_heads", f"{H}: head dimension {hd}; gd_attention_small_fwd serves multiples of 4 from 4 to 64")
+        mlp = need(blk, "mlp", where + ".")
+        fc1, fc2 = need(mlp, "fc1", where + ".mlp."), need(mlp, "fc2", where + ".mlp.")
+        if not _exact_gelu(getattr(mlp, "act", None)):
+            fail(where + ".mlp.act", f"{getattr(mlp, 'act', None)}: the GEMM epilogue serves exact (erf) GELU")
+        if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear)) or fc1.in_features != D or fc2.in_features != fc1.out_features or \
+                fc2.out_features != D or fc1.out_features % 4:
+            fail(where + ".mlp", f"fc1 / fc2 do not map {D} -> hidden (a multiple of 4) -> {D}")
+        w, b = f32(at.in_proj_weight), _lin_bias(at.in_proj_bias, 3 * D, at.in_proj_weight)
+        p = dict(H=H, cross=cross, norm1=_ln_params(need(blk, "norm1", where + "."), where + ".norm1", fail, D),
+                 norm2=_ln_params(need(blk, "norm2", where + "."), where + ".norm2", fail, D),
+                 out=(f32(at.out_proj.weight), _lin_bias(at.out_proj.bias, D, at.in_proj_weight)),
+                 fc1=(f32(fc1.weight), _lin_bias(fc1.bias, fc1.out_features, fc1.weight)), fc2=(f32(fc2.weight), _lin_bias(fc2.bias, D, fc2.weight)))
+        if cross:
+            p["norm_context"] = _ln_params(need(blk, "norm_context", where + "."), where + ".norm_context", fail, D)
+            p["q"], p["kv"] = (w[:D].contiguous(), b[:D].contiguous()), (w[D:].contiguous(), b[D:].contiguous())
+        else:
+            p["qkv"] = (w, b)
+        return p
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    def _to(self, device):
+        if self.flow_head[0].device == device:
+            return
+        mv = lambda v: v.to(device) if torch.is_tensor(v) else tuple(mv(u) for u in v) if isinstance(v, tuple) else v
+        for n in ("input_norm", "output_norm", "input_transform", "flow_head"):
+            setattr(self, n, mv(getattr(self, n)))
+        if self.virtual is not None:
+            self.virtual = self.virtual.to(device)
+        for blocks in (self.time_blocks, self.space_virtual_blocks, self.space_point2virtual_blocks, self.space_virtual2point_blocks):
+            for p in blocks:
+                for k in p:
+                    p[k] = mv(p[k])
+
+    def _ln(self, x, p):
+        self.launches += 1
+        return ops.layernorm_fwd(x, p[0], p[1], p[2], save_stats=False)[0]
+
+    def _gemm(self, a, p, **kw):
+        self.launches += 1
+        return ops.gemm_nt(a, p[0], bias=p[1], **kw)
+
+    def _attend(self, q, k, v, seq_q, seq_k, H):
+        """q [rows_q, >= D], k, v [rows_k, >= D] (column blocks; equal row strides within each) under their sequence layouts -> o [rows_q, D]."""
+        D = self.D
+        G0, G1, Lq, r0, r1, rl = seq_q
+        _, _, Lk, c0, c1, cl = seq_k
+        view = lambda t, L, a, b, c: torch.as_strided(t, (G0, G1, L, D), (a * t.stride(0), b * t.stride(0), c * t.stride(0), 1), t.storage_offset())
+        o = torch.empty(q.shape[0], D, dtype=torch.float32, device=q.device)
+        self.launches += 1
+        ops.attention_small_fwd(view(q, Lq, r0, r1, rl), view(k, Lk, c0, c1, cl), view(v, Lk, c0, c1, cl), G0, G1, Lq, Lk, H, out=view(o, Lq, r0, r1, rl))
+        return o
+
+    def _tail(self, p, xn, o, out, accumulate):
+        x1 = self._gemm(o, p["out"], residual=xn)                                           # the residual is the NORMED x (modules.py:174-183)
+        f = self._gemm(self._ln(x1, p["norm2"]), p["fc1"], act=1)
+        return self._gemm(f, p["fc2"], residual=x1, out=out, accumulate=accumulate)
+
+    def self_block(self, p, x, seq, out=None, accumulate=False):
+        """AttnBlock.forward on the rows x [R, D] (contiguous) under the sequence layout `seq`; the result replaces x, or goes (added, with
+        accumulate) to `out` [R, D]."""
+        D = self.D
+        xn = self._ln(x, p["norm1"])
+        qkv = self._gemm(xn, p["qkv"])
+        o = self._attend(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], seq, seq, p["H"])
+        return self._tail(p, xn, o, x if out is None else out, accumulate)
+
+    def cross_block(self, p, x, ctx, seq, seq_ctx, out=None, accumulate=False):
+        """CrossAttnBlock.forward: the rows x [R, D] attend to the rows ctx [Rc, D]."""
+        D = self.D
+        xn = self._ln(x, p["norm1"])
+        q = self._gemm(xn, p["q"])
+        kv = self._gemm(self._ln(ctx, p["norm_context"]), p["kv"])
+        o = self._attend(q, kv[:, :D], kv[:, D:], seq, seq_ctx, p["H"])
+        return self._tail(p, xn, o, x if out is None else out, accumulate)
+
+    @torch.no_grad()
+    def __call__(self, x, mask=None):
+        if mask is not None:
+            raise GdHipError(f"FusedUpdateFormer: {self.name}: a mask is not served")
+        if x.dim() != 4 or x.shape[3] != self.Din or not x.is_cuda or x.dtype != torch.float32:
+            raise GdHipError(f"FusedUpdateFormer: {self.name}: x {tuple(x.shape)} {x.dtype} on {x.device} is not fp32 [B, N, S, {self.Din}] on the GPU")
+        self._to(x.device)
+        B, N, S, _ = x.shape
+        D, nv, M = self.D, self.nv, B * N * S
+        n = N + nv
+        self.launches = 0
+        fin = self._gemm(self._ln(x.reshape(M, self.Din), self.input_norm), self.input_transform).view(B, N * S, D)       # init_tokens; the result grows on it
+        tok = torch.empty(B, n, S, D, dtype=torch.float32, device=x.device)
+        tok[:, :N].copy_(fin.view(B, N, S, D))
+        if nv:
+            tok[:, N:].copy_(self.virtual.expand(nv, S, D))                                  # once per call
+        self.launches += 2 if nv else 1
+        rows = tok.view(B, n * S, D)
+        pts, virt = rows[:, :N * S], rows[:, N * S:]
+        seq_p, seq_v = (1, S, N, 0, 1, S), (1, S, nv, 0, 1, S)
+        nt, j = len(self.time_blocks), 0
+        for i, p in enumerate(self.time_blocks):
+            space = nv > 0 and i % self.every == 0
+            last = i == nt - 1
+            if last and not space:                                                            # the virtual rows are dead: the point rows alone, onto fin
+                for b in range(B):
+                    self.self_block(p, pts[b], (N, 1, S, S, 0, 1), out=fin[b], accumulate=True)
+                break
+            self.self_block(p, tok.view(B * n * S, D), (B * n, 1, S, S, 0, 1))
+            if space:
+                for b in range(B):
+                    self.cross_block(self.space_virtual2point_blocks[j], virt[b], pts[b], seq_v, seq_p)
+                    self.self_block(self.space_virtual_blocks[j], virt[b], seq_v)
+                    self.cross_block(self.space_point2virtual_blocks[j], pts[b], virt[b], seq_p, seq_v, out=fin[b] if last else None, accumulate=last)
+                j += 1
+        y = self._ln(fin.view(M, D), self.output_norm)
+        delta = self._gemm(y, self.flow_head)
+        return delta.view(B, N, S, self.ldo)[..., :self.Dout], None
+
+
 class TrackState:
     """What one call carries from iteration to iteration.  coords [B, N, S, 2] (map cells) and track_feats [B, N, S, C] are in the loop's row order;
     `load` / `coords_bsn` / `feats_bsn` translate from and to the module's [B, S, N, .]."""
@@ -79,9 +306,10 @@ class FusedTracker:
     """FusedTracker(tracker).forward(query_points, fmaps, iters, ...) -> what the module's forward returns.  fp32 only (see the module docstring:
     a 16-bit mode is not offered).  The parameters are read and packed once, here, on whatever device the module is on (build it after loading the
     checkpoint); if that is not the device of the feature map handed to `begin` / `forward`, the packed copies are moved there on that call (`_to`).
-    The user's `updateformer` is called as it stands and must itself live on the feature map's device."""
+    The user's `updateformer` is called as it stands and must itself live on the feature map's device; fused_updateformer=True (off by default) runs
+    it as a FusedUpdateFormer instead, read and refused here like everything else."""
 
-    def __init__(self, tracker, name="tracker"):
+    def __init__(self, tracker, name="tracker", fused_updateformer=False):
         self.name = name
 
         def fail(attr, why):
@@ -136,6 +364,10 @@ class FusedTracker:
         self._gemm_ok("ffeat_updater[0]", C, fail)
         self.ffeat_updater = (f32(mods[0].weight), self._bias(mods[0]))
         self.updateformer = need(tracker, "updateformer")
+        if fused_updateformer:
+            self.updateformer = FusedUpdateFormer(self.updateformer, name=f"{name}.updateformer")
+            if self.updateformer.Din != self.D or self.updateformer.Dout != C + 2:
+                fail("updateformer", f"maps {self.updateformer.Din} -> {self.updateformer.Dout}, not {self.D} -> {C + 2}")
         qrt = need(tracker, "query_ref_token")
         if tuple(qrt.shape) != (1, 2, self.D):
             fail("query_ref_token", f"{tuple(qrt.shape)}, not (1, 2, {self.D})")

@@ -84,6 +84,18 @@ int gd_attention_bwd(const void* qkv, const void* o, const void* dout, const flo
 int gd_cross_attention_fwd(const void* q, const void* kv, void* o, float* lse, int B, int Nq, int Nk, int H, int head_dim,
                            long ldq, long ldkv, float scale, int dtype, void* stream);
 
+/* Multi-head attention forward for SHORT sequences of any small head dimension, exact fp32, addressed by strides: the VGGT tracker's update
+ * transformer (vggt/heads/track_modules/modules.py:170-218, AttnBlock / CrossAttnBlock on torch.nn.MultiheadAttention between its input and
+ * output projections).  o = softmax(scale q k^T) v per (sequence, head); no mask, no dropout, no lse.  Sequence g = (g0 < G0, g1 < G1); row i of
+ * its q sits at q + g0 * sq0 + g1 * sq1 + i * ldq, head h is columns [h * head_dim, (h + 1) * head_dim); k, v (Nk rows) and o (Nq rows) are
+ * addressed the same way with their own strides, so q, k and v may be column blocks of one packed tensor and a sequence's tokens need not be
+ * neighbours in memory.  head_dim a multiple of 4 from 4 to 64; Nq, Nk >= 1 otherwise free (keys are walked in tiles with an online softmax);
+ * every stride a non-negative multiple of 4 elements, row strides >= H * head_dim; pointers 16-byte aligned; the range o spans overlaps the range
+ * of none of the inputs.  Deterministic (no atomics).  Anything else is refused before any launch. */
+int gd_attention_small_fwd(const float* q, const float* k, const float* v, float* o, int G0, int G1, int Nq, int Nk, int H, int head_dim,
+                           long ldq, long ldk, long ldv, long ldo, long sq0, long sq1, long sk0, long sk1, long sv0, long sv1, long so0,
+                           long so1, float scale, void* stream);
+
 /* LoRA backward of one block in one pass (utils/model.py:57-71): dt [M,8] f32 = dqv [M,K] . bt^T and gbt [8,K] f32 += t^T . dqv for
  * the bf16 (dq, dv) gradient block dqv (row stride ldx elements), t [M,8] f32 the saved rank projections, bt [8,K] bf16 the B factors
  * transposed.  bt == NULL: only the second product (dt may be NULL too) — any [8, K] += t^T . X with an [M, 8] f32 left operand, e.g. the

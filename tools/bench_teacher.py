@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -35,7 +35,12 @@
    every iteration, as the reference does), the same with the table cached on the device, and teacher_tracker.FusedTracker (NCHW and channel-last input);
    gd_corr_sample alone with the bytes per second of the in-map window cells it gathers; the update transformer's share of the fused time.
    "vggt_tracker_share_of_targets" (--sections tracker_share): the teacher of heads_share with a real tracker behind the 128-feature head, fused_blocks
-   and fused_heads on: `targets()` and the tracker call alone with fused_tracker off and on.
+   and fused_heads on: `targets()` and the tracker call alone with fused_tracker off and on, and with fused_updateformer on top.
+8. "vggt_updateformer" (--sections updateformer): the tracker's update transformer alone at teacher size — B = 1, N = 300 points + 64 virtual tracks, S = 2, hidden
+   384, depth 6 + 6, 8 heads, random weights: the torch module of tests/tracker_layout.py against teacher_tracker.FusedUpdateFormer, alternating, each twice;
+   the launches of one fused call; gd_attention_small_fwd alone for the four shapes it is called with (device events around 50 back-to-back calls); every GEMM
+   of one fused call by shape, from device events around each launch; one LayerNorm over all rows.  "vggt_tracker" also times FusedTracker with
+   fused_updateformer (alternating with the plain fused tracker).
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -114,11 +119,14 @@ def main():
         tracker_section(res, a, dev)
     if "tracker_share" in sections:
         tracker_share_section(res, a, dev)
+    if "updateformer" in sections:
+        updateformer_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
            "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
-           "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"]}
+           "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"],
+           "updateformer": ["vggt_updateformer"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -237,7 +245,7 @@ def tracker_section(res, a, dev):
     trk = teacher_size_tracker(dev)
     cached = teacher_size_tracker(dev, cache_pos_embed=True)
     cached.load_state_dict(trk.state_dict())
-    fused = FusedTracker(trk)
+    fused, fused_uf = FusedTracker(trk), FusedTracker(trk, fused_updateformer=True)
     fmaps = torch.randn(1, S, 128, H, W, device=dev)
     cl = fmaps.permute(0, 1, 3, 4, 2).contiguous()
     q = torch.rand(1, N, 2, device=dev) * torch.tensor([2.0 * (W - 1), 2.0 * (H - 1)], device=dev)
@@ -245,14 +253,18 @@ def tracker_section(res, a, dev):
     def module_run(m):
         with torch.no_grad():
             return m(q, fmaps, iters=iters)
-    out = dict(t, updateformer="the torch module in every path", dtype="float32")
+    out = dict(t, updateformer="the torch module in every path but fused_updateformer*", dtype="float32")
     want, got = module_run(cached)[0][-1], fused(q, fmaps, iters=iters)[0][-1]
     out["fused_vs_module_final_coords_max_abs_px"] = float((want - got).abs().max())       # random unit-scale weights: the loop amplifies rounding
     # the host-built table costs seconds per call: fewer windows for that path
     out["module_host_table"] = timed(lambda: module_run(trk), 1, min(a.iters, 3))
     for name, fn in (("module_cached_table", lambda: module_run(cached)), ("fused", lambda: fused(q, fmaps, iters=iters)),
-                     ("fused_channel_last", lambda: fused(q, iters=iters, fmaps_cl=cl))):
+                     ("fused_channel_last", lambda: fused(q, iters=iters, fmaps_cl=cl)), ("fused_updateformer", lambda: fused_uf(q, fmaps, iters=iters)),
+                     ("fused_again", lambda: fused(q, fmaps, iters=iters)), ("fused_updateformer_again", lambda: fused_uf(q, fmaps, iters=iters))):
         out[name] = timed(fn, a.warm, a.iters)
+    out["fused_updateformer_vs_module_final_coords_max_abs_px"] = float((want - fused_uf(q, fmaps, iters=iters)[0][-1]).abs().max())
+    out["speedup_fused_updateformer_vs_fused"] = round(min(out["fused"]["median_ms"], out["fused_again"]["median_ms"]) /
+                                                       min(out["fused_updateformer"]["median_ms"], out["fused_updateformer_again"]["median_ms"]), 3)
     st = fused.begin(q, fmaps)
     out["corr_sample"] = timed(lambda: ops.corr_sample(st.pyramid, st.feats, st.coords, fused.radius, ld=fused.kpad), a.warm, a.iters, reps=20)
     cells = 0                                   # the in-map cells of every (2r+2)^2 window: what the kernel's dot products read (512 B each)
@@ -297,8 +309,9 @@ def tracker_share_section(res, a, dev):
                                    "track_head": track.eval(), "camera_head": lambda self, toks: [torch.zeros(1, 2, 9, device=dev)]})()
     img = torch.rand(1, S, 3, (a.img // 14) * 14, (a.img // 14) * 14, device=dev)
     out = dict(TRACKER, width=C, depth=a.depth, aggregator="fused_blocks bf16", heads="fused_heads f32")
-    for tag, on in (("module_tracker", False), ("fused_tracker", True)):
-        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=on)
+    for tag, on, uf in (("module_tracker", False, False), ("fused_tracker", True, False), ("fused_tracker_fused_updateformer", True, True)):
+        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=on,
+                              fused_updateformer=uf)
         toks, ps, _ = r.aggregate(img)
         fm, pitch = r.heads["track_head.feature_extractor"](toks, img, ps, channel_last=True)
         nchw = fm.permute(0, 1, 4, 2, 3)
@@ -313,6 +326,72 @@ def tracker_share_section(res, a, dev):
         out[tag]["tracker_share_of_targets"] = round(out[tag]["tracker"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
         del r
     res["vggt_tracker_share_of_targets"] = out
+
+
+def updateformer_section(res, a, dev):
+    """The tracker's update transformer alone at teacher size with random weights: the user's module against FusedUpdateFormer (alternating, each
+    twice), gd_attention_small_fwd alone for the four shapes the transformer calls it with, and the per-kernel split of one fused call."""
+    import tracker_layout as TL
+    from gd_amd.teacher_tracker import FusedUpdateFormer
+    t = TRACKER
+    S, N, D, depth, H = t["S"], t["N"], t["hidden_size"], t["depth"], 8
+    with torch.device(dev):
+        m = TL.UpdateFormerLayout(depth, depth, 3 * 128 + 4, D, 130, num_heads=H).eval()
+    fused = FusedUpdateFormer(m)
+    x = torch.randn(1, N, S, 388, device=dev)
+
+    def module_run():
+        with torch.no_grad():
+            return m(x)[0]
+    out = dict(B=1, N=N, S=S, hidden=D, depth=depth, heads=H, virtual_tracks=fused.nv, dtype="float32")
+    want, got = module_run(), fused(x)[0]
+    out["max_abs_diff_vs_module"], out["max_abs_module"] = float((want - got).abs().max()), float(want.abs().max())
+    out["launches_per_call"] = fused.launches
+    paths = {"module": module_run, "fused": lambda: fused(x)}
+    for name, fn in paths.items():
+        out[name] = timed(fn, a.warm, a.iters)
+    for name, fn in paths.items():
+        out[name + "_again"] = timed(fn, 1, a.iters)
+    best = lambda k: min(out[k]["median_ms"], out[k + "_again"]["median_ms"])
+    out["speedup_fused_vs_module"] = round(best("module") / best("fused"), 3)
+    # the attention kernel alone, on the views the transformer hands it
+    n, nv = N + fused.nv, fused.nv
+    qkv, q1, kv = torch.randn(n * S, 3 * D, device=dev), torch.randn(n * S, D, device=dev), torch.randn(n * S, 2 * D, device=dev)
+    o = torch.empty(n * S, D, device=dev)
+    view = lambda tns, c0, r0, G0, G1, L, a0, a1, al: torch.as_strided(tns, (G0, G1, L, D), (a0 * tns.stride(0), a1 * tns.stride(0), al * tns.stride(0), 1),
+                                                                      r0 * tns.stride(0) + c0)
+    shapes = {
+        "time": ((qkv, 0, 0, n, 1, S, S, 0, 1), (qkv, D, 0, n, 1, S, S, 0, 1), (qkv, 2 * D, 0, n, 1, S, S, 0, 1), (o, 0, 0, n, 1, S, S, 0, 1)),
+        "virtual2point": ((q1, 0, N * S, 1, S, nv, 0, 1, S), (kv, 0, 0, 1, S, N, 0, 1, S), (kv, D, 0, 1, S, N, 0, 1, S), (o, 0, N * S, 1, S, nv, 0, 1, S)),
+        "virtual": ((qkv, 0, N * S, 1, S, nv, 0, 1, S), (qkv, D, N * S, 1, S, nv, 0, 1, S), (qkv, 2 * D, N * S, 1, S, nv, 0, 1, S), (o, 0, N * S, 1, S, nv, 0, 1, S)),
+        "point2virtual": ((q1, 0, 0, 1, S, N, 0, 1, S), (kv, 0, N * S, 1, S, nv, 0, 1, S), (kv, D, N * S, 1, S, nv, 0, 1, S), (o, 0, 0, 1, S, N, 0, 1, S)),
+    }
+    out["attention_small"] = {}
+    for name, (aq, ak, av, ao) in shapes.items():
+        vq, vk, vv, vo = view(*aq), view(*ak), view(*av), view(*ao)
+        G0, G1, Lq, Lk = vq.shape[0], vq.shape[1], vq.shape[2], vk.shape[2]
+        r = timed(lambda: ops.attention_small_fwd(vq, vk, vv, G0, G1, Lq, Lk, H, out=vo), a.warm, a.iters, reps=50)
+        r.update(G0=G0, G1=G1, Nq=Lq, Nk=Lk, calls_per_transformer=depth, flop=4 * G0 * G1 * Lq * Lk * D)
+        out["attention_small"][name] = r
+    out["attention_small_us_per_transformer_call"] = round(sum(v["median_ms"] * depth for v in out["attention_small"].values()) * 1e3, 1)
+    # the per-kernel split of one fused call: device events around every GEMM (ops.GemmProfiler), LayerNorm and attention by their own timing
+    prof = ops.GemmProfiler()
+    ops.set_gemm_profiler(prof)
+    fused(x)
+    ops.set_gemm_profiler(None)
+    torch.cuda.synchronize()
+    flop, _, launches = prof.totals()
+    by = {}
+    for e0, e1, fl, tag in prof.records:
+        k = f"M={tag[0]} N={tag[1]} K={tag[2]} {tag[4]}"
+        d = by.setdefault(k, {"calls": 0, "ms": 0.0})
+        d["calls"] += 1
+        d["ms"] = round(d["ms"] + e0.elapsed_time(e1), 4)
+    out["fused_gemm"] = {"flop": flop, "launches": launches, "event_ms_total": round(sum(d["ms"] for d in by.values()), 3), "by_shape": by}
+    xn = torch.randn(n * S, D, device=dev)
+    g, b = torch.ones(D, device=dev), torch.zeros(D, device=dev)
+    out["layernorm_all_rows"] = timed(lambda: ops.layernorm_fwd(xn, g, b, 1e-5, save_stats=False), a.warm, a.iters, reps=50)
+    res["vggt_updateformer"] = out
 
 
 MAST3R_HEAD = dict(enc_dim=1024, dec_dim=768, feature_dim=256, last_dim=128, local_feat_dim=24, two_confs=True)
