@@ -1168,6 +1168,13 @@ template <typename T> static void attn_bwd_launch(const AttnBwdArgs& a, DkvForm 
     else attn_dkv_launch<T, true>(a, f);
 }
 
+// delta_ws of gd_attention_bwd: [2][B * H][Npad] floats (-delta | -lse2), Npad = N rounded up to whole 64-query tiles (what the kernels call npad)
+extern "C" size_t gd_attention_bwd_workspace_bytes(int B, int N, int H) {
+    if (B <= 0 || N <= 0 || H <= 0) return 0;
+    const size_t npad = ((size_t)N + 63) / 64 * 64;
+    return 2 * (size_t)B * (size_t)H * npad * sizeof(float);
+}
+
 extern "C" int gd_attention_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
                                 float* delta_ws, int B, int N, int H, int head_dim, float scale, int dtype,
                                 int grad_order, void* stream) {
