@@ -372,7 +372,9 @@ __device__ __forceinline__ CvpTile cvp_tile(int l, int tiles) {
 template <typename T> __device__ __forceinline__ void cv_st4(T* p, f32x4 v);
 template <> __device__ __forceinline__ void cv_st4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
 template <> __device__ __forceinline__ void cv_st4<bf16>(bf16* p, f32x4 v) { *(bf16x4*)p = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]}; }
-template <> __device__ __forceinline__ void cv_st4<f16>(f16* p, f32x4 v) { *(f16x4*)p = f16x4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]}; }
+// (saturating, like from_f32<f16> in the tile kernels: G inv overflows fp16 where an inverse norm is huge — a zero feature row has inv = 1e12 — and an
+//  infinity there meets that row's zero features in the contraction: inf * 0 = NaN in every gradient row of the pair.  +-65504 * 0 = 0, the exact term.)
+template <> __device__ __forceinline__ void cv_st4<f16>(f16* p, f32x4 v) { *(f16x4*)p = f16_sat4(v[0], v[1], v[2], v[3]); }
 
 // The two epilogues of the persistent kernel, from the accumulators (wave tile 32 x 64: rows wm*32 + ib*16 + 4g + r, columns wn*64 + 4c + jb).
 __device__ __forceinline__ void cvp_epilogue_fwd(const f32x4 (&acc)[2][4], const f32x4 (&t1v)[2][4], const f32x4 (&t2v)[2][4], const f32x4* sSt, float* sP,

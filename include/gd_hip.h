@@ -117,8 +117,14 @@ int gd_lora_bwd_fused_scaled(const void* dqv, long ldx, const float* t, const vo
  * src/finetune_timm_mast3r.py:504-540 variant 1) = F.normalize + bmm x2 + softmax + get_masked_patch_cost
  * (utils/functions.py:402-422) + kl_divergence_map (utils/losses.py:5-15).
  * f1,f2 [P,hw,C] raw features; t1,t2 [P,hw,ldt] f32 teacher maps with row stride ldt >= hw elements (ldt % 4 == 0 gives
- * 16-byte aligned rows: the fast path; pad entries are never read as data); m1,m2 [P,hw] uint8 row masks;
- * loss [P] f32; stats [P,2,hw,4] f32 (saved for the backward).
+ * 16-byte aligned rows: the fast path; the pad entries hw..ldt-1 of a row must be finite — zero, as pad_teacher_maps writes them: the
+ * persistent kernels load them next to the last columns and multiply them by a zeroed score; no kernel writes them); m1,m2 [P,hw] uint8 row masks;
+ * loss [P] f32; stats [P,2,hw,4] f32 = per (pair, view, row) {inv_norm, max(teacher rowsum, 1e-8), logZ, W}, saved for the backward.  The dense
+ * forwards write all four fields of every row, masked rows included; gd_cost_volume_kl_fwd_rows writes inv_norm and rowsum of every row but logZ
+ * and W of the KEPT rows only (a masked row's keep what the buffer held) — every backward selects by the mask and never reads a masked row's
+ * logZ / W, so either forward's stats feed either backward.  Nothing read from a workspace was left there by an earlier call: the backward's
+ * G pad columns (hw..round_up(hw, 64)-1) and the kept-row form's rows past the kept count are written as zeros by the kernels themselves.
+ * A zero feature row has inv_norm = 1e12: its scores are 0, its gradient inv_norm * (dloss/d normalised row), finite in every engine.
  * tstats [P,2,hw,4] f32 = per teacher row {max(rowsum, 1e-8), W = sum_j t, A = sum_j t log t, 0} with
  * t = max(T / rowsum, 1e-8): it depends on the teacher maps only, so a caller that caches a pair's targets computes it once
  * with gd_cost_volume_teacher_stats and every step then reads each map a single time; tstats == NULL: computed inside. */
