@@ -428,3 +428,156 @@ extern "C" int gd_l2norm_bwd(const float* y, const float* dy, const float* inv, 
     GD_LAUNCH_OK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The two ends of the VGGT teacher's DINOv2 patch embedder (vggt/layers/vision_transformer.py:217-236, 274-278; vggt/models/aggregator.py:216-242)
+// ---------------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(2))) long i64x2;
+
+template <typename T> __device__ __forceinline__ void load8f(const T* p, f32x4& a, f32x4& b);
+template <> __device__ __forceinline__ void load8f<float>(const float* p, f32x4& a, f32x4& b) { a = *(const f32x4*)p; b = *(const f32x4*)(p + 4); }
+template <> __device__ __forceinline__ void load8f<bf16>(const bf16* p, f32x4& a, f32x4& b) {
+    const bf16x8 t = *(const bf16x8*)p;
+    a = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+    b = f32x4{(float)t[4], (float)t[5], (float)t[6], (float)t[7]};
+}
+
+// out [BS, 1 + R + Np, D] fp32: row 0 = cls + pos[0], rows 1..R = reg (no position), row 1 + R + i = float(patch[b Np + i]) + pos[1 + i].
+// A thread moves 8 columns (one 16-byte bf16 load, 16-byte fp32 loads and stores); every element is one fp32 addition or a copy.
+template <typename T>
+__global__ __launch_bounds__(256) void dino_assemble_kernel(const T* patch, const float* cls, const float* reg, const float* pos, float* out, int BS,
+                                                            int Np, int R, int D) {
+    const int cpr = D / 8, Nt = 1 + R + Np;
+    const long total = (long)BS * Nt * cpr;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % cpr) * 8;
+        const long t = i / cpr;
+        const int b = (int)(t / Nt), tok = (int)(t % Nt);
+        f32x4 a0, a1;
+        if (tok >= 1 && tok <= R) {
+            load8f<float>(reg + (long)(tok - 1) * D + c, a0, a1);
+        } else {
+            const int p = tok == 0 ? 0 : tok - R;                    // the position row: 0 for cls, 1 + i for patch i
+            f32x4 p0, p1;
+            load8f<float>(pos + (long)p * D + c, p0, p1);
+            if (tok == 0) load8f<float>(cls + c, a0, a1);
+            else load8f<T>(patch + ((long)b * Np + (tok - 1 - R)) * D + c, a0, a1);
+            a0 += p0;
+            a1 += p1;
+        }
+        float* o = out + t * D + c;
+        *(f32x4*)o = a0;
+        *(f32x4*)(o + 4) = a1;
+    }
+}
+
+// One patch row on one wave: ln_fwd_kernel<float, float, NV>'s row body — the same operations in the same order, so that one error bound
+// (tests/rowwise_ref64.ln_fwd_bound) serves both — without the statistics outputs.
+template <int NV>
+__device__ __forceinline__ void ln_row_f32(const float* xr, const float* gamma, const float* beta, float* yr, int D, float eps, int lane) {
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < D) {
+            v[i] = load4<float>(xr + c);
+            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
+        }
+    }
+    const float mu = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < D) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float d = v[i][k] - mu; q += d * d; }
+        }
+    }
+    const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < D) {
+            const f32x4 g = *(const f32x4*)(gamma + c), b = *(const f32x4*)(beta + c);
+            f32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (v[i][k] - mu) * rs * g[k] + b[k];
+            store4n<float>(yr + c, o);
+        }
+    }
+}
+
+// One wave per output row of tokens [B S, 1 + Rg + gh gw, D]: a prefix row is a copy of the frame's camera / register token (slot 0 for the first
+// frame of a batch entry, slot 1 for the others), a patch row is ln_row_f32 of the embedder's row 1 + R + i (its cls and register rows are never
+// read); lane 0 writes the row's (y, x) position as one 16-byte store.
+template <int NV>
+__global__ __launch_bounds__(256) void vggt_tokens_from_dino_kernel(const float* x, const float* gamma, const float* beta, float eps,
+                                                                    const float* camera, const float* regs, float* tokens, long* pos, long rows,
+                                                                    int S, int gw, int Np, int R, int Rg, int D) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int P = 1 + Rg + Np;
+    const long f = row / P;
+    const int t = (int)(row - f * P);
+    float* out = tokens + row * D;
+    i64x2 yx = {0, 0};
+    if (t <= Rg) {
+        const int slot = (f % S) ? 1 : 0;
+        const float* src = t == 0 ? camera + (long)slot * D : regs + ((long)slot * Rg + (t - 1)) * D;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (lane + 64 * i) * 4;
+            if (c < D) *(f32x4*)(out + c) = *(const f32x4*)(src + c);
+        }
+    } else {
+        const int i = t - 1 - Rg;
+        ln_row_f32<NV>(x + (f * (1 + R + Np) + 1 + R + i) * D, gamma, beta, out, D, eps, lane);
+        yx = i64x2{(long)(i / gw + 1), (long)(i % gw + 1)};
+    }
+    if (lane == 0) *(i64x2*)(pos + row * 2) = yx;
+}
+
+#define GD_ALIGNED16(p) (((uintptr_t)(p) & 15) == 0)
+
+extern "C" int gd_dino_assemble_tokens(const void* patch, int patch_dtype, const float* cls, const float* reg, const float* pos, float* out, int BS,
+                                       int Np, int R, int D, void* stream) {
+    GD_REQUIRE(D > 0 && D % 8 == 0, "gd_dino_assemble_tokens: D=%d must be a multiple of 8", D);
+    GD_REQUIRE(BS > 0 && Np > 0 && R >= 0, "gd_dino_assemble_tokens: bad shape BS=%d Np=%d R=%d", BS, Np, R);
+    GD_REQUIRE(patch_dtype == GD_F32 || patch_dtype == GD_BF16, "gd_dino_assemble_tokens: patch is f32 or bf16 (patch_dtype %d)", patch_dtype);
+    GD_REQUIRE(patch && cls && pos && out && (reg || R == 0), "gd_dino_assemble_tokens: null pointer (reg may be null only when R = 0)");
+    GD_REQUIRE(GD_ALIGNED16(patch) && GD_ALIGNED16(out) && GD_ALIGNED16(cls) && GD_ALIGNED16(reg) && GD_ALIGNED16(pos),
+               "gd_dino_assemble_tokens: patch, cls, reg, pos and out must be 16-byte aligned");
+    const long total = (long)BS * (1 + R + Np) * (D / 8);
+    const dim3 grid((unsigned)(total < 256L * 65536 ? (total + 255) / 256 : 65536)), blk(256);
+    if (patch_dtype == GD_BF16)
+        hipLaunchKernelGGL(dino_assemble_kernel<bf16>, grid, blk, 0, (hipStream_t)stream, (const bf16*)patch, cls, reg, pos, out, BS, Np, R, D);
+    else
+        hipLaunchKernelGGL(dino_assemble_kernel<float>, grid, blk, 0, (hipStream_t)stream, (const float*)patch, cls, reg, pos, out, BS, Np, R, D);
+    GD_LAUNCH_OK();
+    return 0;
+}
+
+extern "C" int gd_vggt_tokens_from_dino(const float* x, const float* gamma, const float* beta, float eps, const float* camera, const float* regs,
+                                        float* tokens, long* pos, int B, int S, int gh, int gw, int R, int Rg, int D, void* stream) {
+    GD_REQUIRE(D > 0 && D % 8 == 0 && D <= 64 * 4 * LN_MAXV, "gd_vggt_tokens_from_dino: D=%d must be a multiple of 8 and <= 2048", D);
+    GD_REQUIRE(B > 0 && S > 0 && gh > 0 && gw > 0 && R >= 0 && Rg >= 0, "gd_vggt_tokens_from_dino: bad shape B=%d S=%d grid=%dx%d R=%d Rg=%d", B, S, gh,
+               gw, R, Rg);
+    GD_REQUIRE((long)gh * gw + R + Rg + 1 < (1L << 30) && (long)B * S < (1L << 30), "gd_vggt_tokens_from_dino: token count out of range");
+    GD_REQUIRE(x && gamma && beta && camera && tokens && pos && (regs || Rg == 0), "gd_vggt_tokens_from_dino: null pointer (regs may be null only when Rg = 0)");
+    GD_REQUIRE(GD_ALIGNED16(x) && GD_ALIGNED16(gamma) && GD_ALIGNED16(beta) && GD_ALIGNED16(camera) && GD_ALIGNED16(regs) && GD_ALIGNED16(tokens) &&
+                   GD_ALIGNED16(pos),
+               "gd_vggt_tokens_from_dino: x, gamma, beta, camera, regs, tokens and pos must be 16-byte aligned");
+    const int Np = gh * gw;
+    const long rows = (long)B * S * (1 + Rg + Np);
+    GD_REQUIRE((rows + 3) / 4 < (1L << 31), "gd_vggt_tokens_from_dino: %ld rows exceed the grid", rows);
+    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+#define T_FD(NV) hipLaunchKernelGGL((vggt_tokens_from_dino_kernel<NV>), grid, blk, 0, s, x, gamma, beta, eps, camera, regs, tokens, pos, rows, S, gw, Np, R, Rg, D)
+    LN_DISPATCH_NV(D, T_FD);
+#undef T_FD
+    GD_LAUNCH_OK();
+    return 0;
+}

@@ -1761,3 +1761,49 @@ def track_update(delta, coords, mul1=1.0, mul2=1.0):
     dfeat = torch.empty(B * N * S, C, dtype=torch.float32, device=d.device)
     check(lib().gd_track_update(ptr(d), d.stride(0), ptr(coords), ptr(pred), ptr(dfeat), B, S, N, C, float(mul1), float(mul2), stream()), "gd_track_update")
     return pred, dfeat
+
+
+# ------------------------------------------------------------------------------------------------ DINOv2 patch embedder ends (csrc/norm.hip)
+def dino_assemble_tokens(patch, cls, reg, pos, BS, Np, out=None):
+    """patch [BS * Np, D] f32 | bf16, cls [D], reg [R, D] or None, pos [1 + Np, D] (fp32) -> out fp32 [BS, 1 + R + Np, D]: cls + pos[0] | reg |
+    patch + pos[1:] (gd_dino_assemble_tokens)."""
+    D = patch.shape[-1]
+    R = 0 if reg is None else reg.shape[0]
+    _req(patch.is_cuda and patch.is_contiguous() and tuple(patch.shape) == (BS * Np, D), f"dino_assemble_tokens: patch must be a contiguous CUDA tensor {(BS * Np, D)}")
+    _f32c(cls, (D,), "dino_assemble_tokens: cls")
+    _f32c(pos, (1 + Np, D), "dino_assemble_tokens: pos")
+    if reg is not None:
+        _f32c(reg, (R, D), "dino_assemble_tokens: reg")
+    if out is None:
+        out = torch.empty(BS, 1 + R + Np, D, dtype=torch.float32, device=patch.device)
+    else:
+        _f32c(out, (BS, 1 + R + Np, D), "dino_assemble_tokens: out")
+    check(lib().gd_dino_assemble_tokens(ptr(patch), dtype_code(patch), ptr(cls), ptr(reg), ptr(pos), ptr(out), BS, Np, R, D, stream()),
+          "gd_dino_assemble_tokens")
+    return out
+
+
+def vggt_tokens_from_dino(x, gamma, beta, eps, camera, regs, B, S, gh, gw, R, tokens=None, pos=None):
+    """x fp32 [B * S, 1 + R + gh * gw, D] (the embedder's residual stream after its last block), camera [2, D], regs [2, Rg, D] or None ->
+    (tokens fp32 [B * S, 1 + Rg + gh * gw, D], pos int64 [B * S, 1 + Rg + gh * gw, 2]): the aggregator's block inputs (gd_vggt_tokens_from_dino)."""
+    D = x.shape[-1]
+    Rg = 0 if regs is None else regs.shape[1]
+    P = 1 + Rg + gh * gw
+    _f32c(x, (B * S, 1 + R + gh * gw, D), "vggt_tokens_from_dino: x")
+    _f32c(gamma, (D,), "vggt_tokens_from_dino: gamma")
+    _f32c(beta, (D,), "vggt_tokens_from_dino: beta")
+    _f32c(camera, (2, D), "vggt_tokens_from_dino: camera")
+    if regs is not None:
+        _f32c(regs, (2, Rg, D), "vggt_tokens_from_dino: regs")
+    if tokens is None:
+        tokens = torch.empty(B * S, P, D, dtype=torch.float32, device=x.device)
+    else:
+        _f32c(tokens, (B * S, P, D), "vggt_tokens_from_dino: tokens")
+    if pos is None:
+        pos = torch.empty(B * S, P, 2, dtype=torch.int64, device=x.device)
+    else:
+        _req(pos.is_cuda and pos.dtype == torch.int64 and pos.is_contiguous() and tuple(pos.shape) == (B * S, P, 2),
+             f"vggt_tokens_from_dino: pos must be a contiguous CUDA int64 tensor {(B * S, P, 2)}")
+    check(lib().gd_vggt_tokens_from_dino(ptr(x), ptr(gamma), ptr(beta), float(eps), ptr(camera), ptr(regs), ptr(tokens), ptr(pos), B, S, gh, gw, R, Rg, D,
+                                         stream()), "gd_vggt_tokens_from_dino")
+    return tokens, pos

@@ -1,5 +1,6 @@
 """The two frozen teachers' transformer stacks on the HIP kernels instead of the user's PyTorch modules: the VGGT aggregator
-(FusedAggregatorBlocks, below) and the MASt3R / CroCo encoder and two-sided decoder (FusedCroCoBlocks, at the end).
+(FusedAggregatorBlocks, below), the DINOv2 patch embedder inside it (FusedDinoEmbed, after it) and the MASt3R / CroCo encoder and two-sided
+decoder (FusedCroCoBlocks, at the end).
 
 The VGGT teacher's alternating-attention stack (vggt/models/aggregator.py:246-275: `aa_block_size` frame blocks on [B*S, P], then
 `aa_block_size` global blocks on [B, S*P], `depth / aa_block_size` times) on the HIP kernels instead of the user's PyTorch modules.
@@ -36,37 +37,42 @@ def fold_layer_scale(linear, ls):
 class _BlockParams:
     """One block's tensors in the form the kernels take: matrices in the operand dtype, vectors in fp32."""
 
-    def __init__(self, blk, name, dtype):
+    def __init__(self, blk, name, dtype, who="FusedAggregatorBlocks", rotary=True):
+        """rotary=False (the DINOv2 embedder's blocks): no q/k norm and no RoPE between the QKV GEMM and attention, so both must be absent."""
         def need(obj, attr, where):
             if not hasattr(obj, attr):
-                raise GdHipError(f"FusedAggregatorBlocks: {name}: {where} has no `{attr}`")
+                raise GdHipError(f"{who}: {name}: {where} has no `{attr}`")
             return getattr(obj, attr)
         attn, mlp = need(blk, "attn", "the block"), need(blk, "mlp", "the block")
         H = int(need(attn, "num_heads", "attn"))
         C = need(attn, "qkv", "attn").weight.shape[1]
         if C % H or C // H != 64:
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
+            raise GdHipError(f"{who}: {name}: head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
         scale = float(getattr(attn, "scale", 64 ** -0.5))
         if abs(scale - 64 ** -0.5) > 1e-9:
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: attn.scale {scale} is not 64^-0.5")
+            raise GdHipError(f"{who}: {name}: attn.scale {scale} is not 64^-0.5")
         qn, kn = need(attn, "q_norm", "attn"), need(attn, "k_norm", "attn")
         ln = [isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (64,) for m in (qn, kn)]
         ident = [isinstance(m, torch.nn.Identity) for m in (qn, kn)]
+        if not rotary and not all(ident):
+            raise GdHipError(f"{who}: {name}: attn.q_norm / attn.k_norm are {type(qn).__name__} / {type(kn).__name__}: served is Identity on both")
         if not (all(ln) or all(ident)):
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: q_norm / k_norm are {type(qn).__name__} / {type(kn).__name__}: served are "
+            raise GdHipError(f"{who}: {name}: q_norm / k_norm are {type(qn).__name__} / {type(kn).__name__}: served are "
                              "LayerNorm(64) with affine on both, or Identity on both")
         if all(ln) and qn.eps != kn.eps:
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: q_norm and k_norm differ in eps")
+            raise GdHipError(f"{who}: {name}: q_norm and k_norm differ in eps")
         rope = getattr(attn, "rope", None)
-        if rope is None:
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: attn.rope is None: the fused q/k step always rotates")
+        if rotary and rope is None:
+            raise GdHipError(f"{who}: {name}: attn.rope is None: the fused q/k step always rotates")
+        if not rotary and rope is not None:
+            raise GdHipError(f"{who}: {name}: attn.rope is {type(rope).__name__}: these blocks run without a rotary step")
         act = getattr(mlp, "act", None)           # vggt/layers/mlp.py: act_layer(); a layout without the attribute calls F.gelu itself
         if act is not None and not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
-            raise GdHipError(f"FusedAggregatorBlocks: {name}: mlp.act is {act}: the GEMM epilogue serves exact (erf) GELU")
+            raise GdHipError(f"{who}: {name}: mlp.act is {act}: the GEMM epilogue serves exact (erf) GELU")
         for nm in ("norm1", "norm2"):
             m = need(blk, nm, "the block")
             if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (C,)):
-                raise GdHipError(f"FusedAggregatorBlocks: {name}: {nm} is not an affine LayerNorm({C})")
+                raise GdHipError(f"{who}: {name}: {nm} is not an affine LayerNorm({C})")
         f32 = lambda t: None if t is None else t.detach().float().contiguous()
         op = lambda t: t.detach().to(dtype).contiguous()
         self.H, self.C = H, C
@@ -150,6 +156,178 @@ class FusedAggregatorBlocks:
                     nsel += 1
                 outputs.append(torch.cat([inter[k].view(B, S, P, C), x.view(B, S, P, C)], dim=-1))
         return outputs, maps
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The VGGT aggregator's DINOv2 patch embedder (vggt/layers/vision_transformer.py; vggt/models/aggregator.py:151-186, 206-242)
+# ----------------------------------------------------------------------------------------------------------------------------------
+class FusedDinoEmbed:
+    """FusedDinoEmbed(embedder, dtype=torch.bfloat16, name="aggregator.patch_embed"): the aggregator's `patch_embed` when it is a DINOv2 ViT
+    (`dinov2_vitl14_reg`: 24 blocks of width 1024 on 1 + 4 + gh * gw tokens per frame) on the HIP kernels.  The module stays the user's: its
+    parameters are read once, here (duck-typed on the reference's attribute names), and anything the kernels do not serve is refused naming
+    the attribute.
+
+    One block runs as layernorm_fwd -> gemm_nt(+bias) -> attention_fwd -> gemm_nt(+bias, +residual) -> layernorm_fwd -> gemm_nt(+bias, GELU) ->
+    gemm_nt(+bias, +residual): no q/k norm and no rotary step, LayerScale folded into proj / fc2, the residual stream in fp32.  The ends are
+    gd_patch_im2col (normalisation fused) + the patch GEMM + gd_dino_assemble_tokens, and the final norm (gd_layernorm_fwd for `forward`, fused
+    with the aggregator's token and position assembly in gd_vggt_tokens_from_dino for `aggregator_tokens`).
+
+    dtype as FusedAggregatorBlocks: torch.bfloat16 = bf16 operands, fp32 accumulation; torch.float32 = exact fp32, the parity mode.
+
+    The position table at the table's own square grid is `pos_embed`; for any other (H, W) the module's own `interpolate_pos_encoding` runs
+    once on a shape-only stand-in and its fp32 result is cached per (H, W) (as vit.GDViT does for a foreign resampler): the bicubic /
+    antialias / offset arithmetic stays the user's, exactly."""
+
+    WHO = "FusedDinoEmbed"
+
+    def __init__(self, embedder, dtype=torch.bfloat16, name="aggregator.patch_embed"):
+        who = self.WHO
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise GdHipError(f"{who}: dtype must be torch.float32 or torch.bfloat16")
+
+        def need(obj, attr, where):
+            if not hasattr(obj, attr):
+                raise GdHipError(f"{who}: {where} has no `{attr}`")
+            return getattr(obj, attr)
+        blocks = getattr(embedder, "blocks", None)
+        if blocks is None:
+            raise GdHipError(f"{who}: {name} has no `blocks` (the 'conv' patch embedder is one convolution: leave fused_patch_embed off)")
+        if getattr(embedder, "chunked_blocks", False):
+            raise GdHipError(f"{who}: {name}.chunked_blocks is true: served is a flat block list (block_chunks=0)")
+        pos_embed = need(embedder, "pos_embed", name)
+        D = int(pos_embed.shape[-1])
+        if D % 8 or D > 2048:
+            raise GdHipError(f"{who}: {name}.pos_embed has width {D}: served is a multiple of 8 up to 2048")
+        P = need(embedder, "patch_size", name)
+        P = int(P[0] if isinstance(P, (tuple, list)) else P)
+        proj = need(need(embedder, "patch_embed", name), "proj", f"{name}.patch_embed")
+        if not (isinstance(proj, torch.nn.Conv2d) and tuple(proj.kernel_size) == (P, P) and tuple(proj.stride) == (P, P) and
+                tuple(proj.padding) == (0, 0) and tuple(proj.dilation) == (1, 1) and proj.groups == 1 and proj.in_channels == 3 and
+                proj.out_channels == D):
+            raise GdHipError(f"{who}: {name}.patch_embed.proj is {proj}: served is Conv2d(3, {D}, kernel_size={P}, stride={P})")
+        if not isinstance(getattr(embedder.patch_embed, "norm", None), (torch.nn.Identity, type(None))):
+            raise GdHipError(f"{who}: {name}.patch_embed.norm is {type(embedder.patch_embed.norm).__name__}: served is Identity")
+        R = int(need(embedder, "num_register_tokens", name))
+        reg = getattr(embedder, "register_tokens", None)
+        if (0 if reg is None else int(reg.shape[-2])) != R or (reg is not None and int(reg.shape[-1]) != D):
+            raise GdHipError(f"{who}: {name}.register_tokens {None if reg is None else tuple(reg.shape)} disagrees with num_register_tokens = {R} at width {D}")
+        cls = need(embedder, "cls_token", name)
+        if cls.numel() != D:
+            raise GdHipError(f"{who}: {name}.cls_token {tuple(cls.shape)} is not one token of width {D}")
+        if not callable(getattr(embedder, "interpolate_pos_encoding", None)):
+            raise GdHipError(f"{who}: {name} has no `interpolate_pos_encoding`")
+        norm = need(embedder, "norm", name)
+        if not (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and tuple(norm.normalized_shape) == (D,)):
+            raise GdHipError(f"{who}: {name}.norm is not an affine LayerNorm({D})")
+        self.blocks = [_BlockParams(b, f"{name}.blocks[{i}]", dtype, who=who, rotary=False) for i, b in enumerate(blocks)]
+        for i, p in enumerate(self.blocks):
+            if p.C != D:
+                raise GdHipError(f"{who}: {name}.blocks[{i}]: width {p.C} is not the embedder's {D}")
+        f32 = lambda t: t.detach().float().contiguous()
+        self.embedder, self.name, self.dtype, self.D, self.P, self.R = embedder, name, dtype, D, P, R
+        K = 3 * P * P
+        self.Kp = (K + 63) // 64 * 64                                 # the patch convolution as a [D, Kp] matrix (vit.GDViT._patch_plan)
+        wp = torch.zeros(D, self.Kp, dtype=torch.float32, device=proj.weight.device)
+        wp[:, :K] = proj.weight.detach().float().reshape(D, K)
+        self.wpe, self.bpe = wp.to(dtype).contiguous(), None if proj.bias is None else f32(proj.bias)
+        self.cls = f32(cls).reshape(D)
+        self.reg = None if reg is None else f32(reg).reshape(R, D)
+        self.norm = (f32(norm.weight), f32(norm.bias), float(norm.eps))
+        self._pos_cache, self._agg_norm = {}, None
+
+    # -- pieces ---------------------------------------------------------------------------------------------------------------------
+    def _pos(self, H, W, gh, gw):
+        """fp32 [1 + gh * gw, D]: `pos_embed` at its own square grid, else the module's own resampling (called as the module calls it: (tokens, w, h)
+        with w the image's FIRST spatial extent), once per (H, W)."""
+        key = (H, W)
+        if key not in self._pos_cache:
+            pe = self.embedder.pos_embed
+            if not (gh * gw == pe.shape[1] - 1 and H == W):
+                with torch.no_grad():
+                    pe = self.embedder.interpolate_pos_encoding(torch.empty(1, 1 + gh * gw, self.D, device=pe.device, dtype=torch.float32), H, W)
+            if tuple(pe.shape) != (1, 1 + gh * gw, self.D):
+                raise GdHipError(f"{self.WHO}: {self.name}.interpolate_pos_encoding returned {tuple(pe.shape)}, expected {(1, 1 + gh * gw, self.D)}")
+            self._pos_cache[key] = pe.detach().float()[0].contiguous()
+        return self._pos_cache[key]
+
+    def _block(self, p, x, B, N):
+        """x [B*N, D] fp32 residual stream -> the same after one block (attention_fwd reads the packed qkv as the GEMM wrote it)."""
+        dt = self.dtype
+        y, _, _ = ops.layernorm_fwd(x, p.n1[0], p.n1[1], p.n1[2], save_stats=False, out_dtype=dt)
+        qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
+        o, _ = ops.attention_fwd(qkv, B, N, p.H)
+        x = ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x)
+        y, _, _ = ops.layernorm_fwd(x, p.n2[0], p.n2[1], p.n2[2], save_stats=False, out_dtype=dt)
+        h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
+        return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x)
+
+    def _grid(self, H, W):
+        if H % self.P or W % self.P or H < self.P or W < self.P:
+            raise GdHipError(f"{self.WHO}: {self.name}: image {H} x {W} is not a multiple of patch_size = {self.P}")
+        return H // self.P, W // self.P
+
+    # -- entry points -----------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def features(self, img, mean=None, std=None):
+        """img [BS, 3, H, W] fp32 -> the residual stream after the last block, fp32 [BS, 1 + R + Np, D] (`x_prenorm`).  With `mean` and `std`
+        (three floats each) the image is in [0, 1] and is normalised inside gd_patch_im2col; without them it is already normalised."""
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise GdHipError(f"{self.WHO}: {self.name}: images {tuple(img.shape)}, expected [BS, 3, H, W]")
+        if (mean is None) != (std is None):
+            raise GdHipError(f"{self.WHO}: {self.name}: pass both mean and std or neither")
+        BS, _, H, W = img.shape
+        gh, gw = self._grid(H, W)
+        Np, Nt = gh * gw, 1 + self.R + gh * gw
+        col = ops.patch_im2col(img, H, W, self.P, self.Kp, (0.0, 0.0, 0.0) if mean is None else mean, (1.0, 1.0, 1.0) if std is None else std, self.dtype)
+        tok = ops.gemm_nt(col, self.wpe, bias=self.bpe)
+        x = ops.dino_assemble_tokens(tok, self.cls, self.reg, self._pos(H, W, gh, gw), BS, Np).view(BS * Nt, self.D)
+        for p in self.blocks:
+            x = self._block(p, x, BS, Nt)
+        return x.view(BS, Nt, self.D)
+
+    @torch.no_grad()
+    def forward(self, img, masks=None):
+        """The module's `forward` (forward_features, vision_transformer.py:262-281) on an already normalised image: its dict, for shadowing."""
+        if masks is not None:
+            raise GdHipError(f"{self.WHO}: {self.name}: masks are not served")
+        x = self.features(img)
+        BS, Nt, D = x.shape
+        xn = ops.layernorm_fwd(x.view(BS * Nt, D), *self.norm, save_stats=False, out_dtype=torch.float32)[0].view(BS, Nt, D)
+        return {"x_norm_clstoken": xn[:, 0], "x_norm_regtokens": xn[:, 1:self.R + 1], "x_norm_patchtokens": xn[:, self.R + 1:], "x_prenorm": x,
+                "masks": None}
+
+    def check_aggregator(self, aggregator):
+        """-> (camera [2, D], regs [2, Rg, D] or None, prefix) of an aggregator this embedder can feed; refuses, naming the attribute, otherwise."""
+        who = self.WHO
+        for a in ("camera_token", "register_token", "patch_start_idx", "_resnet_mean", "_resnet_std"):
+            if not hasattr(aggregator, a):
+                raise GdHipError(f"{who}: the aggregator has no `{a}`")
+        prefix = int(aggregator.patch_start_idx)
+        if prefix < 1:
+            raise GdHipError(f"{who}: aggregator.patch_start_idx = {prefix}: served is a camera token (and registers) in front of the patches")
+        cam, reg = aggregator.camera_token, aggregator.register_token
+        if cam.shape[-1] != self.D or tuple(cam.shape[:3]) != (1, 2, 1):
+            raise GdHipError(f"{who}: aggregator.camera_token {tuple(cam.shape)}: the embedder's width is {self.D} (expected [1, 2, 1, {self.D}])")
+        if tuple(reg.shape) != (1, 2, prefix - 1, self.D):
+            raise GdHipError(f"{who}: aggregator.register_token {tuple(reg.shape)} does not fit patch_start_idx = {prefix} at width {self.D}")
+        f32 = lambda t: t.detach().float().contiguous()
+        return f32(cam).reshape(2, self.D), (f32(reg).reshape(2, prefix - 1, self.D) if prefix > 1 else None), prefix
+
+    @torch.no_grad()
+    def aggregator_tokens(self, images, aggregator):
+        """images [B, S, 3, H, W] in [0, 1] -> (tokens fp32 [B*S, P, D], pos int64 [B*S, P, 2]): what the aggregator hands its first frame block
+        (aggregator.py:206-242: normalisation, the embedder, its final norm on the patch rows, camera / register tokens, the position grid),
+        without the module."""
+        camera, regs, _ = self.check_aggregator(aggregator)
+        if images.dim() != 5 or images.shape[2] != 3:
+            raise GdHipError(f"{self.WHO}: images {tuple(images.shape)}, expected [B, S, 3, H, W]")
+        B, S, _, H, W = images.shape
+        gh, gw = self._grid(H, W)
+        if self._agg_norm is None or self._agg_norm[0] is not aggregator:
+            self._agg_norm = (aggregator, [float(v) for v in aggregator._resnet_mean.flatten().tolist()],
+                              [float(v) for v in aggregator._resnet_std.flatten().tolist()])
+        x = self.features(images.reshape(B * S, 3, H, W), self._agg_norm[1], self._agg_norm[2])
+        return ops.vggt_tokens_from_dino(x, *self.norm, camera, regs, B, S, gh, gw, self.R)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -11,8 +11,8 @@ PyTorch-ROCm inference).  What lives here is the glue around them:
 * `VGGTTeacherRunner` — `extract_vggt_features` + `sample_keypoints` (src/finetune_timm_vggt.py:357-449) as one call that returns the
   pair's targets in the cache layout; the reference aggregator's hard-wired `return_attn=True` is neutralised for the duration of the
   call (the selected blocks return a 1-element placeholder instead of the maps); with `fused_heads` the three dense-prediction heads run on
-  the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules, and with `fused_tracker` the tracker's tail runs on
-  teacher_tracker.FusedTracker;
+  the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules, with `fused_tracker` the tracker's tail runs on
+  teacher_tracker.FusedTracker, and with `fused_patch_embed` the aggregator's DINOv2 patch embedder runs on teacher_blocks.FusedDinoEmbed;
 * `MASt3RTeacherRunner` — `extract_mast3r_features` + `filter_and_match_keypoints` + the depth branch
   (src/finetune_timm_mast3r.py:345-469, 617-633) around the user's `dust3r.inference.inference`.
 """
@@ -103,7 +103,7 @@ class VGGTTeacherRunner:
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
     def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32,
-                 fused_updateformer=False, fused_tracker=False):
+                 fused_updateformer=False, *, fused_patch_embed=False, fused_tracker=False):
         if fused_updateformer and not fused_tracker:
             raise GdHipError("VGGTTeacherRunner: fused_updateformer=True needs fused_tracker=True (the fused update transformer runs inside FusedTracker's loop)")
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
@@ -125,12 +125,23 @@ class VGGTTeacherRunner:
                                                                                       ("track_head.feature_extractor", vggt.track_head.feature_extractor))}
         # fused_tracker: the tracker's correlation pyramid, window sampling, position embedding, glue and small MLPs run on the HIP kernels
         # (teacher_tracker.FusedTracker, fp32; the update transformer stays the user's module unless fused_updateformer, off by default, hands it to
-        # teacher_tracker.FusedUpdateFormer; pass both by keyword, fused_tracker stays the last one).  Independent of fused_blocks and fused_heads; a tracker the
+        # teacher_tracker.FusedUpdateFormer; pass both by keyword, fused_tracker stays the last one — keyword only since fused_patch_embed, which is keyword only,
+        # stands in front of it).  Independent of fused_blocks and fused_heads; a tracker the
         # class refuses raises here, not in targets().
         self.tracker = None
         if fused_tracker:
             from .teacher_tracker import FusedTracker
             self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker", fused_updateformer=fused_updateformer)
+
+        # fused_patch_embed (keyword only): the aggregator's DINOv2 patch embedder runs on the HIP kernels (teacher_blocks.FusedDinoEmbed, operand type
+        # `dtype`).  Independent of the other switches; an embedder, or an aggregator around it, that the class refuses raises here, not in targets().
+        self.embed = None
+        if fused_patch_embed:
+            from .teacher_blocks import FusedDinoEmbed
+            if not hasattr(agg, "patch_embed"):
+                raise GdHipError("VGGTTeacherRunner: fused_patch_embed=True: the aggregator has no `patch_embed`")
+            self.embed = FusedDinoEmbed(agg.patch_embed, dtype=dtype, name="aggregator.patch_embed")
+            self.embed.check_aggregator(agg)
 
     def _block_inputs(self, rgb_vggt):
         """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the
@@ -161,13 +172,23 @@ class VGGTTeacherRunner:
         agg = self.m.aggregator
         if self.fused is not None:
             B, S = rgb_vggt.shape[:2]
-            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda and self.dtype != torch.float32):
-                tokens, pos = self._block_inputs(rgb_vggt)
+            if self.embed is not None:
+                tokens, pos = self.embed.aggregator_tokens(rgb_vggt, agg)         # neither the aggregator's forward nor the module's is called
+            else:
+                with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda and self.dtype != torch.float32):
+                    tokens, pos = self._block_inputs(rgb_vggt)
             tokens_list, maps = self.fused.forward(tokens, pos, B, S)
             return tokens_list, agg.patch_start_idx, maps
-        with QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
-            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
-                tokens_list, ps_idx, _ = agg(rgb_vggt)
+        # with fused_patch_embed, for this call only, an instance attribute shadows the embedder's forward: the user's aggregator drives the fused embedder
+        if self.embed is not None:
+            agg.patch_embed.forward = self.embed.forward
+        try:
+            with QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
+                with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
+                    tokens_list, ps_idx, _ = agg(rgb_vggt)
+        finally:
+            if self.embed is not None:
+                del agg.patch_embed.forward          # the class's own forward is visible again
         qk = [(q.to(self.dtype) if q.dtype not in (torch.float32, torch.bfloat16) else q,
                k.to(self.dtype) if k.dtype not in (torch.float32, torch.bfloat16) else k) for q, k in cap.pairs()]
         return tokens_list, ps_idx, qk

@@ -651,6 +651,25 @@ int gd_track_assemble(const float* coords, const float* corr, const float* feats
 int gd_track_update(const float* delta, long ldd, float* coords, float* pred, float* dfeat, int B, int S, int N, int C, float mul1, float mul2,
                     void* stream);
 
+/* The two ends of the VGGT teacher's DINOv2 patch embedder (teacher_blocks.FusedDinoEmbed); the 24 blocks between them run on gd_layernorm_fwd,
+ * gd_gemm_nt and gd_attention_fwd.  Both are one launch on `stream`, allocate nothing, and refuse arguments outside their contract before any launch.
+ * gd_dino_assemble_tokens: prepare_tokens_with_masks without masks (vggt/layers/vision_transformer.py:217-236) -> out fp32 [BS, 1 + R + Np, D]:
+ *   row 0 = cls + pos[0]; rows 1..R = reg[r] (the registers get no position); row 1 + R + i = float(patch[b * Np + i]) + pos[1 + i].
+ *   patch [BS * Np, D] f32 | bf16 (patch_dtype), cls [D], reg [R, D] (NULL allowed when R = 0), pos [1 + Np, D], all fp32.  Every output element is
+ *   one fp32 addition or a copy.  D % 8 == 0; every pointer 16-byte aligned.
+ * gd_vggt_tokens_from_dino: the embedder's final norm on its patch rows (vision_transformer.py:274-278) and the aggregator's token and position
+ *   assembly (vggt/models/aggregator.py:216-242, slice_expand_and_flatten :326-349).  x fp32 [B * S, 1 + R + gh * gw, D] is the embedder's residual
+ *   stream after its last block; for frame f = b * S + s, slot = 0 when s == 0 and 1 otherwise:
+ *     tokens[f, 0] = camera[slot];  tokens[f, 1 + r] = regs[slot, r];  tokens[f, 1 + Rg + i] = LayerNorm(x[f, 1 + R + i]; gamma, beta, eps)
+ *     pos[f, 0 .. Rg] = (0, 0);     pos[f, 1 + Rg + y * gw + xx] = (y + 1, xx + 1)
+ *   camera fp32 [2, D], regs fp32 [2, Rg, D] (NULL allowed when Rg = 0), tokens fp32 [B * S, 1 + Rg + gh * gw, D], pos int64 [B * S, 1 + Rg + gh * gw, 2].
+ *   The embedder's cls and register rows are never read.  A normalised row takes the operations of gd_layernorm_fwd's fp32 path in the same
+ *   order.  D % 8 == 0 and D <= 2048; every pointer 16-byte aligned. */
+int gd_dino_assemble_tokens(const void* patch, int patch_dtype, const float* cls, const float* reg, const float* pos, float* out, int BS, int Np,
+                            int R, int D, void* stream);
+int gd_vggt_tokens_from_dino(const float* x, const float* gamma, const float* beta, float eps, const float* camera, const float* regs, float* tokens,
+                             long* pos, int B, int S, int gh, int gw, int R, int Rg, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

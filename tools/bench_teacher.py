@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer,patch_embed,patch_embed_share]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -41,6 +41,11 @@
    the launches of one fused call; gd_attention_small_fwd alone for the four shapes it is called with (device events around 50 back-to-back calls); every GEMM
    of one fused call by shape, from device events around each launch; one LayerNorm over all rows.  "vggt_tracker" also times FusedTracker with
    fused_updateformer (alternating with the plain fused tracker).
+9. "vggt_patch_embed" (--sections patch_embed): the aggregator's DINOv2 patch embedder alone at teacher size — ViT-L/14, 24 blocks of width 1024, 16 heads, 4
+   registers, two frames of 518^2 (1374 tokens each), random weights: teacher_blocks.FusedDinoEmbed (f32 and bf16 operands) against the torch module of
+   tests/dino_layout.py (f32, and under bf16 autocast), alternating, each path twice; the agreement of every path with the f32 module.
+   "vggt_patch_embed_share" (--sections patch_embed_share): the teacher of tracker_share built around that embedder instead of the stub convolution, everything
+   else fused: the embedder alone, `aggregate` and `targets()` with fused_patch_embed off and on.
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -121,12 +126,16 @@ def main():
         tracker_share_section(res, a, dev)
     if "updateformer" in sections:
         updateformer_section(res, a, dev)
+    if "patch_embed" in sections:
+        patch_embed_section(res, a, dev)
+    if "patch_embed_share" in sections:
+        patch_embed_share_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
            "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
            "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"],
-           "updateformer": ["vggt_updateformer"]}
+           "updateformer": ["vggt_updateformer"], "patch_embed": ["vggt_patch_embed"], "patch_embed_share": ["vggt_patch_embed_share"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -286,14 +295,16 @@ def tracker_section(res, a, dev):
     res["vggt_tracker"] = out
 
 
-def tracker_share_section(res, a, dev):
+def vggt_shaped_teacher(a, dev, make_aggregator=AggregatorLayout, **agg_kw):
+    """-> (teacher, track head, image pair): the aggregator at --depth / --width, depth and point heads, and a track head with a 128-feature extractor at
+    down_ratio 2 around a teacher-size tracker, random weights."""
     import dpt_layout as DL
     import tracker_layout as TL
     C, S = a.width, 2
     idx = [a.depth // 6, a.depth // 2 - 1, 3 * a.depth // 4 - 1, a.depth - 1]
     with torch.device(dev):
-        agg = AggregatorLayout(img_size=a.img, patch_size=14, embed_dim=C, depth=a.depth, num_heads=C // 64, num_register_tokens=4,
-                               attn_indices=[a.depth // 2, a.depth - 1], temperature=0.8).eval()
+        agg = make_aggregator(img_size=a.img, patch_size=14, embed_dim=C, depth=a.depth, num_heads=C // 64, num_register_tokens=4,
+                              attn_indices=[a.depth // 2, a.depth - 1], temperature=0.8, **agg_kw).eval()
         head = lambda **kw: DL.DPTLayout(**dict(dict(VGGT_HEAD, dim_in=2 * C), intermediate_layer_idx=idx, **kw)).eval()
         track = TL.TrackHeadLayout(2 * C, levels=TRACKER["levels"], iters=TRACKER["iters"])
         track.feature_extractor = head(features=128, feature_only=True, down_ratio=2)
@@ -308,6 +319,13 @@ def tracker_share_section(res, a, dev):
     teacher = type("Teacher", (), {"aggregator": agg, "depth_head": depth_head, "point_head": point_head,
                                    "track_head": track.eval(), "camera_head": lambda self, toks: [torch.zeros(1, 2, 9, device=dev)]})()
     img = torch.rand(1, S, 3, (a.img // 14) * 14, (a.img // 14) * 14, device=dev)
+    return teacher, track, img
+
+
+def tracker_share_section(res, a, dev):
+    import dpt_layout as DL
+    C = a.width
+    teacher, track, img = vggt_shaped_teacher(a, dev)
     out = dict(TRACKER, width=C, depth=a.depth, aggregator="fused_blocks bf16", heads="fused_heads f32")
     for tag, on, uf in (("module_tracker", False, False), ("fused_tracker", True, False), ("fused_tracker_fused_updateformer", True, True)):
         r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=on,
@@ -326,6 +344,91 @@ def tracker_share_section(res, a, dev):
         out[tag]["tracker_share_of_targets"] = round(out[tag]["tracker"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
         del r
     res["vggt_tracker_share_of_targets"] = out
+
+
+DINO = dict(patch_size=14, embed_dim=1024, depth=24, num_heads=16, num_register_tokens=4)          # dinov2_vitl14_reg
+
+
+def dino_at_teacher_size(a, dev):
+    import dino_layout as DY
+    with torch.device(dev):
+        m = DY.DinoLayout(img_size=a.img, **DINO).eval()
+    for b in m.blocks:                              # random weights: LayerScale below 1 keeps 24 blocks' residual stream in range
+        torch.nn.init.constant_(b.ls1.gamma, 0.2)
+        torch.nn.init.constant_(b.ls2.gamma, 0.2)
+    torch.nn.init.normal_(m.pos_embed, std=0.02)
+    return m
+
+
+def patch_embed_section(res, a, dev):
+    """The DINOv2 patch embedder alone at teacher size: teacher_blocks.FusedDinoEmbed (f32 and bf16 operands) against the torch module of
+    tests/dino_layout.py (f32, and under bf16 autocast; its attention is F.scaled_dot_product_attention), alternating, each path twice."""
+    from gd_amd.teacher_blocks import FusedDinoEmbed
+    m = dino_at_teacher_size(a, dev)
+    side = (a.img // 14) * 14
+    img = torch.randn(2, 3, side, side, device=dev)
+    f32, b16 = FusedDinoEmbed(m, dtype=torch.float32), FusedDinoEmbed(m, dtype=torch.bfloat16)
+
+    def module(autocast, sdpa=True):
+        for b in m.blocks:
+            b.attn.sdpa = sdpa
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            return m(img)
+    Nt = 1 + DINO["num_register_tokens"] + (side // 14) ** 2
+    D, L = DINO["embed_dim"], DINO["depth"]
+    out = dict(DINO, img=side, frames=2, tokens_per_frame=Nt,
+               counted_TFLOP=round(2 * L * (2 * Nt * 12 * D * D + 4 * Nt * Nt * D) / 1e12, 3))          # 12 D^2 per token in the four GEMMs, 4 N D in attention
+    want = module(False, sdpa=False)
+    for k in ("x_prenorm", "x_norm_patchtokens"):
+        out[f"max_abs_{k}"] = {"scale": float(want[k].abs().max()), "fused_f32": T.max_abs(f32.forward(img)[k], want[k]),
+                               "fused_bf16": T.max_abs(b16.forward(img)[k], want[k]), "module_autocast_bf16": T.max_abs(module(True)[k], want[k])}
+    # module_*: attention through F.scaled_dot_product_attention; module_explicit_*: the [B, H, N, N] softmax the reference forms without xformers
+    paths = (("module_f32", lambda: module(False)), ("fused_f32", lambda: f32.forward(img)), ("module_autocast_bf16", lambda: module(True)),
+             ("fused_bf16", lambda: b16.forward(img)), ("module_explicit_f32", lambda: module(False, sdpa=False)),
+             ("module_explicit_autocast_bf16", lambda: module(True, sdpa=False)))
+    for suffix in ("", "_again"):
+        for name, fn in paths:
+            out[name + suffix] = timed(fn, a.warm, a.iters)
+    best = lambda n: min(out[n]["median_ms"], out[n + "_again"]["median_ms"])
+    out["speedup_fused_f32_vs_module_f32"] = round(best("module_f32") / best("fused_f32"), 3)
+    out["speedup_fused_bf16_vs_module_autocast_bf16"] = round(best("module_autocast_bf16") / best("fused_bf16"), 3)
+    out["speedup_fused_bf16_vs_module_explicit_autocast_bf16"] = round(best("module_explicit_autocast_bf16") / best("fused_bf16"), 3)
+    out["fused_bf16_TFLOPs"] = round(out["counted_TFLOP"] / (best("fused_bf16") * 1e-3), 1)
+    res["vggt_patch_embed"] = out
+
+
+def patch_embed_share_section(res, a, dev):
+    """The embedder's share of `aggregate` and of `targets()`: the VGGT-shaped teacher of tracker_share built around the DINO embedder instead of the
+    stub convolution, fused_blocks / fused_heads / fused_tracker on, with fused_patch_embed off and on."""
+    import dino_layout as DY
+    import dpt_layout as DL
+    teacher, track, img = vggt_shaped_teacher(a, dev, DY.DinoAggregatorLayout, dino_depth=DINO["depth"], dino_heads=DINO["num_heads"])
+    emb = teacher.aggregator.patch_embed
+    for b in emb.blocks:
+        b.attn.sdpa = True
+        torch.nn.init.constant_(b.ls1.gamma, 0.2)
+        torch.nn.init.constant_(b.ls2.gamma, 0.2)
+    torch.nn.init.normal_(emb.pos_embed, std=0.02)
+    out = dict(width=a.width, depth=a.depth, embedder=DINO, aggregator="fused_blocks bf16", heads="fused_heads f32", tracker="fused_tracker")
+    frames = ((img - teacher.aggregator._resnet_mean) / teacher.aggregator._resnet_std)[0]
+    for tag, on in (("module_patch_embed", False), ("fused_patch_embed", True)):
+        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=True,
+                              fused_patch_embed=on)
+
+        def embed_run():
+            if on:
+                return r.embed.forward(frames)
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                return emb(frames)
+        got = r.targets(img)
+        out[tag] = {"patch_embed": timed(embed_run, a.warm, a.iters), "aggregate": timed(lambda: r.aggregate(img), 1, a.iters),
+                    "targets": timed(lambda: r.targets(img), 1, min(a.iters, 3)), "targets_returned_none": got is None}
+        out[tag]["patch_embed_share_of_aggregate"] = round(out[tag]["patch_embed"]["median_ms"] / out[tag]["aggregate"]["median_ms"], 3)
+        out[tag]["patch_embed_share_of_targets"] = round(out[tag]["patch_embed"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
+        del r
+    out["speedup_aggregate"] = round(out["module_patch_embed"]["aggregate"]["median_ms"] / out["fused_patch_embed"]["aggregate"]["median_ms"], 3)
+    out["speedup_targets"] = round(out["module_patch_embed"]["targets"]["median_ms"] / out["fused_patch_embed"]["targets"]["median_ms"], 3)
+    res["vggt_patch_embed_share"] = out
 
 
 def updateformer_section(res, a, dev):
