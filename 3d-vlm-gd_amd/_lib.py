@@ -202,6 +202,11 @@ SIGNATURES = {
     "gd_dino_assemble_tokens": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gd_vggt_tokens_from_dino": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_void_p]),
+    "gd_rows_linear": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                               c_int, c_int, c_void_p]),
+    "gd_rows_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_long, c_float, c_void_p]),
+    "gd_adaln_modulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_long, c_float, c_void_p]),
+    "gd_pose_update": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

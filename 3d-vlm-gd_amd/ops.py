@@ -1807,3 +1807,97 @@ def vggt_tokens_from_dino(x, gamma, beta, eps, camera, regs, B, S, gh, gw, R, to
     check(lib().gd_vggt_tokens_from_dino(ptr(x), ptr(gamma), ptr(beta), float(eps), ptr(camera), ptr(regs), ptr(tokens), ptr(pos), B, S, gh, gw, R, Rg, D,
                                          stream()), "gd_vggt_tokens_from_dino")
     return tokens, pos
+
+
+# ------------------------------------------------------------------------------------------------ camera head on a few rows (csrc/rows.hip)
+ROWS_MAX_M, ROWS_LDS_FLOATS = 8, 16384
+
+
+def _f32rows(t, what, cols=None):
+    """A CUDA fp32 2-D view with a contiguous last dim (rows may be strided)."""
+    _req(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and (cols is None or t.shape[1] == cols),
+         f"{what} must be a CUDA fp32 view [rows, {'cols' if cols is None else cols}] with a contiguous last dim, got "
+         f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__} {getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] + (-t.shape[1]) % 4        # the stride of a single row addresses nothing
+
+
+def rows_linear(x, w, bias=None, *, out=None, residual=None, gamma=None, silu=False, gelu=False):
+    """x [M, K] fp32 (M <= 8, rows may be strided), w [N, K] fp32 | bf16 (rows may be strided) -> y [M, N] fp32 =
+    epilogue(prologue(x) w^T) (gd_rows_linear): prologue SiLU(x) with silu=True; epilogue + bias, exact GELU with gelu=True, then
+    residual + gamma * v when residual [M, N] is given (gamma [N] or None = 1).  out= a view to write (default: a new tensor); out may be
+    `residual` itself (in place), never x or w."""
+    ldx = _f32rows(x, "rows_linear: x")
+    M, K = x.shape
+    _req(torch.is_tensor(w) and w.is_cuda and w.dtype in (torch.float32, torch.bfloat16) and w.dim() == 2 and w.shape[1] == K and w.stride(1) == 1,
+         f"rows_linear: w must be a CUDA fp32 | bf16 view [N, {K}] with a contiguous last dim, got {tuple(w.shape) if torch.is_tensor(w) else type(w).__name__} "
+         f"{getattr(w, 'dtype', None)} on {getattr(w, 'device', None)}")
+    N = w.shape[0]
+    ldw = w.stride(0) if N > 1 else K
+    y = torch.empty(M, N + (-N) % 4, dtype=torch.float32, device=x.device)[:, :N] if out is None else out
+    ldy = _f32rows(y, "rows_linear: out", N)
+    _req(y.shape[0] == M, f"rows_linear: out has {y.shape[0]} rows, x has {M}")
+    ldr = 0
+    if residual is not None:
+        ldr = _f32rows(residual, "rows_linear: residual", N)
+        _req(residual.shape[0] == M, f"rows_linear: residual has {residual.shape[0]} rows, x has {M}")
+    for t, what in ((bias, "bias"), (gamma, "gamma")):
+        _req(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (N,)), f"rows_linear: {what} must be a contiguous CUDA fp32 [{N}]")
+    check(lib().gd_rows_linear(ptr(x), ptr(w), dtype_code(w), ptr(y), M, N, K, ldx, ldw, ldy, ptr(bias), ptr(residual), ldr, ptr(gamma), int(bool(silu)),
+                               int(bool(gelu)), stream()), "gd_rows_linear")
+    return y
+
+
+def rows_attention(qkv, B, S, H, scale=None, out=None):
+    """qkv [B * S, 3 * H * hd] fp32 (q | k | v, head-major; rows may be strided) -> o [B * S, H * hd] = softmax(scale q k^T) v per (b, head) over the
+    S <= 8 rows of that batch entry (gd_rows_attention: exact fp32, hd a multiple of 4 up to 256; scale defaults to hd^-0.5)."""
+    ld = _f32rows(qkv, "rows_attention: qkv")
+    _req(qkv.shape[0] == B * S and H >= 1 and qkv.shape[1] % (3 * H) == 0, f"rows_attention: qkv {tuple(qkv.shape)} is not [{B} * {S}, 3 * {H} * hd]")
+    W = qkv.shape[1] // 3
+    hd = W // H
+    o = torch.empty(B * S, W, dtype=torch.float32, device=qkv.device) if out is None else out
+    ldo = _f32rows(o, "rows_attention: out", W)
+    _req(o.shape[0] == B * S, f"rows_attention: out has {o.shape[0]} rows, not {B * S}")
+    check(lib().gd_rows_attention(ptr(qkv), ptr(o), B, S, H, hd, ld, ldo, float(hd ** -0.5 if scale is None else scale), stream()), "gd_rows_attention")
+    return o
+
+
+def adaln_modulate(x, mod, eps=1e-6, out=None):
+    """x [M, D], mod [M, 3 D] = shift | scale | gate (fp32, rows may be strided) -> gate * (LN0(x) * (1 + scale) + shift) + x, LN0 a LayerNorm
+    without affine parameters (gd_adaln_modulate; D a multiple of 4 up to 8192)."""
+    ldx = _f32rows(x, "adaln_modulate: x")
+    M, D = x.shape
+    ldm = _f32rows(mod, "adaln_modulate: mod", 3 * D)
+    o = torch.empty(M, D, dtype=torch.float32, device=x.device) if out is None else out
+    ldo = _f32rows(o, "adaln_modulate: out", D)
+    _req(mod.shape[0] == M and o.shape[0] == M, f"adaln_modulate: x has {M} rows, mod {mod.shape[0]}, out {o.shape[0]}")
+    check(lib().gd_adaln_modulate(ptr(x), ptr(mod), ptr(o), M, D, ldx, ldm, ldo, float(eps), stream()), "gd_adaln_modulate")
+    return o
+
+
+POSE_ACTS = {"linear": 0, "inv_log": 1, "exp": 2, "relu": 3}
+
+
+def pose_update(delta, raw, first, acts=("linear", "linear", "relu"), image_hw=None, enc=None):
+    """delta [M, 9] fp32 (rows may be strided), raw [M, 12] contiguous fp32, updated IN PLACE: raw[:, :9] = (first ? 0 : raw[:, :9]) + delta, columns
+    9..11 stay 0 -> enc [M, 9] = the activated encoding (acts: translation, quaternion, field of view; names of POSE_ACTS); with image_hw = (H, W)
+    also (extrinsic [M, 3, 4], intrinsic [M, 3, 3]) (gd_pose_update)."""
+    ldd = _f32rows(delta, "pose_update: delta", 9)
+    M = delta.shape[0]
+    _f32c(raw, (M, 12), "pose_update: raw")
+    codes = []
+    for a in acts:
+        _req(a in POSE_ACTS, f"pose_update: unknown activation {a!r} (known: {sorted(POSE_ACTS)})")
+        codes.append(POSE_ACTS[a])
+    _req(len(codes) == 3, "pose_update: acts = (translation, quaternion, field of view)")
+    if enc is None:
+        enc = torch.empty(M, 9, dtype=torch.float32, device=delta.device)
+    else:
+        _f32c(enc, (M, 9), "pose_update: enc")
+    E = K = None
+    H = W = 0
+    if image_hw is not None:
+        H, W = int(image_hw[0]), int(image_hw[1])
+        E = torch.empty(M, 3, 4, dtype=torch.float32, device=delta.device)
+        K = torch.empty(M, 3, 3, dtype=torch.float32, device=delta.device)
+    check(lib().gd_pose_update(ptr(delta), ldd, ptr(raw), ptr(enc), ptr(E), ptr(K), M, int(bool(first)), *codes, H, W, stream()), "gd_pose_update")
+    return enc if image_hw is None else (enc, E, K)

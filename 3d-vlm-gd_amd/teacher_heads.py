@@ -22,7 +22,10 @@ The modules stay the user's: these classes read their parameters (duck-typed on 
 once into the operand layout, and refuse, naming the attribute, anything the kernels do not serve.  Off by default
 (teacher_runner.VGGTTeacherRunner(fused_heads=True), teacher_runner.MASt3RTeacherRunner(fused_heads=True)).
 
-_FusedHead holds what the two share: the weight packers, the per-level resize + `layer_rn`, the residual unit and the fusion loop."""
+_FusedHead holds what the two share: the weight packers, the per-level resize + `layer_rn`, the residual unit and the fusion loop.
+
+FusedCameraHead, at the end of the file, is the VGGT teacher's camera head (vggt/heads/camera_head.py) on the few-row kernels of csrc/rows.hip
+(teacher_runner.VGGTTeacherRunner(fused_camera_head=True), off by default): no maps, M = B * S <= 8 token rows and a weight stream."""
 import functools
 
 import torch
@@ -539,5 +542,253 @@ class FusedMASt3RHead(_FusedHead):
             res["conf"] = c
         res["desc"], res["desc_conf"] = d, dc
         return res
+
+    __call__ = forward
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The camera head
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _exact_gelu(m):
+    return isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none"
+
+
+class FusedCameraHead:
+    """FusedCameraHead(camera_head)(tokens_list) -> the module's list of [B, S, 9] encodings (vggt/heads/camera_head.py:83-154 CameraHead), on the
+    few-row kernels of csrc/rows.hip and gd_layernorm_fwd; `poses(tokens_list, image_hw)` also returns the decoded cameras
+    (vggt/utils/pose_enc.py:108-126), written by the last gd_pose_update.
+
+    The head refines M = B * S <= 8 token rows; one call streams every weight `num_iterations` times and is bandwidth-bound.  One iteration is
+        rows_linear (embed_pose, K = 9 padded to 12) -> rows_linear (SiLU prologue, poseLN_modulation) -> adaln_modulate
+        per trunk block: layernorm -> rows_linear (qkv) -> rows_attention -> rows_linear (proj, gamma, in-place residual)
+                         -> layernorm -> rows_linear (fc1, GELU) -> rows_linear (fc2, gamma, in-place residual)
+        layernorm (trunk_norm) -> rows_linear (pose_branch.fc1, GELU) -> rows_linear (pose_branch.fc2) -> pose_update
+    7 + 7 * depth launches, after one layernorm (token_norm) per call that reads the camera rows tokens[:, :, 0] in place through its row stride.
+
+    dtype: the weight type of the trunk and modulation linears.  torch.float32 is the faithful mode (the reference runs this head in fp32, outside
+    autocast); torch.bfloat16 halves the weight stream and is narrower than the reference.  embed_pose and pose_branch stay fp32 in both.
+
+    The module stays the user's: its parameters are read once (duck-typed on the attribute names) and what the kernels do not serve is refused here,
+    naming the attribute.  Off by default (teacher_runner.VGGTTeacherRunner(fused_camera_head=True))."""
+
+    def __init__(self, camera_head, dtype=torch.float32, name="camera_head"):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise GdHipError(f"FusedCameraHead: dtype {dtype}: torch.float32 or torch.bfloat16")
+        self.name, self.dtype, m = name, dtype, camera_head
+
+        def fail(attr, why):
+            raise GdHipError(f"FusedCameraHead: {name}.{attr}: {why}")
+
+        def need(obj, attr, where=""):
+            if getattr(obj, attr, None) is None:
+                fail(where + attr, "missing")
+            return getattr(obj, attr)
+        f32 = lambda t: t.detach().float().contiguous()
+        wt = lambda t: t.detach().to(dtype).contiguous()
+
+        def ln(mod, attr, width):
+            if not (isinstance(mod, torch.nn.LayerNorm) and mod.elementwise_affine and mod.weight is not None and mod.bias is not None) or \
+                    tuple(mod.normalized_shape) != (width,):
+                fail(attr, f"not an affine LayerNorm({width}) with a bias")
+            return (f32(mod.weight), f32(mod.bias), float(mod.eps))
+
+        def linear(mod, attr, k, n=None, cast=f32):
+            if not isinstance(mod, torch.nn.Linear) or mod.in_features != k or (n is not None and mod.out_features != n):
+                fail(attr, f"not a Linear({k} -> {'.' if n is None else n})")
+            b = f32(mod.bias) if mod.bias is not None else None
+            return (cast(mod.weight), b)
+
+        def no_dropout(mod, attr):
+            p = float(getattr(mod, "p", 0.0)) if mod is not None else 0.0
+            if p != 0.0 and getattr(mod, "training", False):
+                fail(attr, f"p = {p} in training mode: the kernels have no dropout")
+
+        def scale(mod, attr, width):
+            if isinstance(mod, torch.nn.Identity):
+                return None
+            g = getattr(mod, "gamma", None)
+            if g is None or tuple(g.shape) != (width,):
+                fail(attr, f"neither Identity nor a LayerScale with gamma [{width}]")
+            return f32(g)
+
+        if int(getattr(m, "target_dim", -1)) != 9:
+            fail("target_dim", f"{getattr(m, 'target_dim', None)}: the pose kernel serves the 9-value absT_quaR_FoV encoding")
+        self.acts = []
+        for a in ("trans_act", "quat_act", "fl_act"):
+            v = getattr(m, a, None)
+            if v not in ops.POSE_ACTS:
+                fail(a, f"{v!r}: known activations are {sorted(ops.POSE_ACTS)}")
+            self.acts.append(v)
+        embed = need(m, "embed_pose")
+        if not isinstance(embed, torch.nn.Linear) or embed.in_features != 9:
+            fail("embed_pose", "not a Linear(9 -> dim)")
+        D = self.D = embed.out_features
+        if D % 8 or D > 2048:
+            fail("embed_pose", f"width {D}: a multiple of 8 up to 2048 is served (gd_layernorm_fwd's row limit)")
+        # embed_pose's K = 9 padded to 12 with zero columns; the raw encoding is kept as [M, 12] rows with columns 9..11 at 0
+        w12 = torch.zeros(D, 12, dtype=torch.float32, device=embed.weight.device)
+        w12[:, :9] = embed.weight.detach().float()
+        self.embed = (w12, f32(embed.bias) if embed.bias is not None else None)
+        ept = need(m, "empty_pose_tokens")
+        if ept.numel() != 9:
+            fail("empty_pose_tokens", f"{tuple(ept.shape)}: not 9 values")
+        self.empty = torch.zeros(1, 12, dtype=torch.float32, device=ept.device)
+        self.empty[0, :9] = ept.detach().float().reshape(9)
+        mod = need(m, "poseLN_modulation")
+        if not (isinstance(mod, torch.nn.Sequential) and len(mod) == 2 and isinstance(mod[0], torch.nn.SiLU)):
+            fail("poseLN_modulation", "not Sequential(SiLU, Linear)")
+        self.modulation = linear(mod[1], "poseLN_modulation[1]", D, 3 * D, wt)
+        an = need(m, "adaln_norm")
+        if not isinstance(an, torch.nn.LayerNorm) or an.elementwise_affine or tuple(an.normalized_shape) != (D,):
+            fail("adaln_norm", f"not a LayerNorm({D}) without affine parameters")
+        self.adaln_eps = float(an.eps)
+        self.token_norm = ln(need(m, "token_norm"), "token_norm", D)
+        self.trunk_norm = ln(need(m, "trunk_norm"), "trunk_norm", D)
+        self.blocks = []
+        for i, blk in enumerate(need(m, "trunk")):
+            w = f"trunk[{i}]."
+            at = need(blk, "attn", w)
+            if getattr(at, "rope", None) is not None:
+                fail(w + "attn.rope", "set: gd_rows_attention has no rotary embedding")
+            for nm in ("q_norm", "k_norm"):
+                if not isinstance(getattr(at, nm, None), torch.nn.Identity):
+                    fail(w + "attn." + nm, f"{type(getattr(at, nm, None)).__name__}: not Identity (qk_norm is not served)")
+            H = int(need(at, "num_heads", w + "attn."))
+            hd = D // H if H >= 1 and D % H == 0 else 0
+            if hd % 4 or not 4 <= hd <= 256:
+                fail(w + "attn.num_heads", f"{H}: head dimension {D / H if H else None}; gd_rows_attention serves multiples of 4 from 4 to 256")
+            no_dropout(getattr(at, "attn_drop", None), w + "attn.attn_drop")
+            no_dropout(getattr(at, "proj_drop", None), w + "attn.proj_drop")
+            mlp = need(blk, "mlp", w)
+            if not _exact_gelu(getattr(mlp, "act", None)):
+                fail(w + "mlp.act", f"{getattr(mlp, 'act', None)}: the epilogue serves exact (erf) GELU")
+            no_dropout(getattr(mlp, "drop", None), w + "mlp.drop")
+            fc1 = linear(need(mlp, "fc1", w + "mlp."), w + "mlp.fc1", D, None, wt)
+            hidden = fc1[0].shape[0]
+            if hidden % 8:
+                fail(w + "mlp.fc1", f"hidden width {hidden}: a multiple of 8 is served")
+            self.blocks.append(dict(H=H, scale=float(getattr(at, "scale", hd ** -0.5)), norm1=ln(need(blk, "norm1", w), w + "norm1", D),
+                                    norm2=ln(need(blk, "norm2", w), w + "norm2", D), qkv=linear(need(at, "qkv", w + "attn."), w + "attn.qkv", D, 3 * D, wt),
+                                    proj=linear(need(at, "proj", w + "attn."), w + "attn.proj", D, D, wt), fc1=fc1,
+                                    fc2=linear(need(mlp, "fc2", w + "mlp."), w + "mlp.fc2", hidden, D, wt),
+                                    ls1=scale(need(blk, "ls1", w), w + "ls1", D), ls2=scale(need(blk, "ls2", w), w + "ls2", D)))
+        if not self.blocks:
+            fail("trunk", "empty")
+        self.hidden = max(b["fc1"][0].shape[0] for b in self.blocks)
+        pb = need(m, "pose_branch")
+        if not _exact_gelu(getattr(pb, "act", None)):
+            fail("pose_branch.act", f"{getattr(pb, 'act', None)}: the epilogue serves exact (erf) GELU")
+        no_dropout(getattr(pb, "drop", None), "pose_branch.drop")
+        self.pb1 = linear(need(pb, "fc1", "pose_branch."), "pose_branch.fc1", D)
+        self.pbh = self.pb1[0].shape[0]
+        if self.pbh % 4:
+            fail("pose_branch.fc1", f"hidden width {self.pbh}: a multiple of 4 is served")
+        self.pb2 = linear(need(pb, "fc2", "pose_branch."), "pose_branch.fc2", self.pbh, 9)
+        self.weight_bytes = sum(t.numel() * t.element_size() for t in self._weights())        # streamed once per iteration
+        self._ws, self.launches = {}, 0
+
+    def _weights(self):
+        yield from (self.embed[0], self.modulation[0], self.pb1[0], self.pb2[0])
+        for b in self.blocks:
+            yield from (b["qkv"][0], b["proj"][0], b["fc1"][0], b["fc2"][0])
+
+    def _to(self, device):
+        if self.empty.device == device:
+            return
+        mv = lambda v: v.to(device) if torch.is_tensor(v) else tuple(mv(u) for u in v) if isinstance(v, tuple) else v
+        for n in ("embed", "empty", "modulation", "token_norm", "trunk_norm", "pb1", "pb2"):
+            setattr(self, n, mv(getattr(self, n)))
+        self.blocks = [{k: mv(v) for k, v in b.items()} for b in self.blocks]
+        self._ws = {}
+
+    def _workspace(self, M, device):
+        """Allocated once per M and reused: the token stream, the operands between the launches, the raw encoding."""
+        ws = self._ws.get(M)
+        if ws is None:
+            D, e = self.D, lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
+            ws = dict(tok=e(M, D), emb=e(M, D), mod=e(M, 3 * D), h=e(M, D), n=e(M, D), qkv=e(M, 3 * D), att=e(M, D), f=e(M, self.hidden), p=e(M, self.pbh),
+                      delta=e(M, 12), raw=torch.zeros(M, 12, dtype=torch.float32, device=device), raw0=self.empty.expand(M, 12).contiguous(), plans={})
+            self._ws[M] = ws
+        return ws
+
+    def _plan(self, ws, B, S, stream):
+        """The launches of one iteration between embed_pose and the pose update as (entry point, arguments, name), built once per (B, S, stream): the
+        head is ~35 short launches per iteration, and the argument checks of the ops wrappers would cost more host time than the kernels run.  The
+        C entry points check every argument again."""
+        key = (B, S, stream)
+        plan = ws["plans"].get(key)
+        if plan is not None:
+            return plan
+        L, ptr, M, D, F32 = ops.lib(), ops.ptr, B * S, self.D, ops._lib.F32
+        tok, emb, mod, h, n, qkv, att, f, p, delta = (ws[k] for k in ("tok", "emb", "mod", "h", "n", "qkv", "att", "f", "p", "delta"))
+
+        def lin(x, wb, y, ldy, res=None, gamma=None, silu=0, gelu=0):
+            w, bias = wb
+            N, K = w.shape
+            return (L.gd_rows_linear, (ptr(x), ptr(w), ops.dtype_code(w), ptr(y), M, N, K, x.stride(0), K, ldy, ptr(bias), ptr(res), ldy if res is not None else 0,
+                                       ptr(gamma), silu, gelu, stream), "gd_rows_linear")
+
+        def ln(x, params, y):
+            g, b, eps = params
+            return (L.gd_layernorm_fwd, (ptr(x), ptr(g), ptr(b), ptr(y), None, None, M, D, D, D, eps, F32, F32, stream), "gd_layernorm_fwd")
+        body = [lin(emb, self.modulation, mod, 3 * D, silu=1),
+                (L.gd_adaln_modulate, (ptr(tok), ptr(mod), ptr(h), M, D, D, 3 * D, D, self.adaln_eps, stream), "gd_adaln_modulate")]
+        for b in self.blocks:
+            body += [ln(h, b["norm1"], n), lin(n, b["qkv"], qkv, 3 * D),
+                     (L.gd_rows_attention, (ptr(qkv), ptr(att), B, S, b["H"], D // b["H"], 3 * D, D, b["scale"], stream), "gd_rows_attention"),
+                     lin(att, b["proj"], h, D, res=h, gamma=b["ls1"]), ln(h, b["norm2"], n), lin(n, b["fc1"], f, self.hidden, gelu=1),
+                     lin(f, b["fc2"], h, D, res=h, gamma=b["ls2"])]
+        body += [ln(h, self.trunk_norm, n), lin(n, self.pb1, p, self.pbh, gelu=1), lin(p, self.pb2, delta, 12)]
+        plan = ws["plans"][key] = dict(first=lin(ws["raw0"], self.embed, emb, D), later=lin(ws["raw"], self.embed, emb, D), body=body)
+        return plan
+
+    @torch.no_grad()
+    def _run(self, tokens_list, num_iterations, image_hw):
+        tokens = tokens_list[-1]
+        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dim() == 4 and tokens.shape[-1] == self.D and tokens.dtype in (torch.float32, torch.bfloat16)):
+            raise GdHipError(f"FusedCameraHead: {self.name}: tokens_list[-1] must be a CUDA fp32 | bf16 tensor [B, S, P, {self.D}], got "
+                             f"{tuple(tokens.shape) if torch.is_tensor(tokens) else type(tokens).__name__} {getattr(tokens, 'dtype', None)} on {getattr(tokens, 'device', None)}")
+        B, S = tokens.shape[:2]
+        M, iters = B * S, int(num_iterations)
+        if M > ops.ROWS_MAX_M:
+            raise GdHipError(f"FusedCameraHead: {self.name}: B * S = {B} * {S} = {M} camera rows; gd_rows_linear serves up to {ops.ROWS_MAX_M}")
+        if M * self.hidden > ops.ROWS_LDS_FLOATS:
+            raise GdHipError(f"FusedCameraHead: {self.name}: B * S = {M} rows of the MLP's {self.hidden} hidden columns exceed the {ops.ROWS_LDS_FLOATS} floats "
+                             "gd_rows_linear stages")
+        if S > 8 or iters < 1:
+            raise GdHipError(f"FusedCameraHead: {self.name}: S = {S}, num_iterations = {num_iterations}")
+        # the camera rows tokens[:, :, 0], read where they lie: row (b, s) sits b * stride(0) + s * stride(1) in; one row stride must address them all
+        ld = tokens.stride(1) if S > 1 else tokens.stride(0)
+        if tokens.stride(3) != 1 or (B > 1 and S > 1 and tokens.stride(0) != S * tokens.stride(1)) or ld % 4 or \
+                tokens.data_ptr() % 16:
+            raise GdHipError(f"FusedCameraHead: {self.name}: tokens_list[-1] with strides {tuple(tokens.stride())}: the camera rows need a contiguous last dim, one "
+                             "row stride (a multiple of 4) over (b, s) and a 16-byte aligned start")
+        self._to(tokens.device)
+        ws, D, stream, L, check = self._workspace(M, tokens.device), self.D, ops.stream(), ops.lib(), ops.check
+        plan = self._plan(ws, B, S, stream)
+        g, b, eps = self.token_norm
+        check(L.gd_layernorm_fwd(tokens.data_ptr(), g.data_ptr(), b.data_ptr(), ws["tok"].data_ptr(), None, None, M, D, ld if M > 1 else D, D, eps,
+                                 ops.dtype_code(tokens), ops._lib.F32, stream), "gd_layernorm_fwd")
+        self.launches += 1 + iters * (len(plan["body"]) + 2)
+        encs, E, K = [], None, None
+        for it in range(iters):
+            for fn, args, what in (plan["first"] if it == 0 else plan["later"],) + tuple(plan["body"]):
+                rc = fn(*args)
+                if rc:
+                    check(rc, what)
+            last = it == iters - 1
+            r = ops.pose_update(ws["delta"][:, :9], ws["raw"], it == 0, self.acts, image_hw if last else None)
+            if last and image_hw is not None:
+                r, E, K = r
+                E, K = E.view(B, S, 3, 4), K.view(B, S, 3, 3)
+            encs.append(r.view(B, S, 9))
+        return encs, E, K
+
+    def forward(self, tokens_list, num_iterations=4):
+        return self._run(tokens_list, num_iterations, None)[0]
+
+    def poses(self, tokens_list, image_hw, num_iterations=4):
+        """-> (the list of [B, S, 9] encodings, extrinsic [B, S, 3, 4], intrinsic [B, S, 3, 3]) of the last iteration, for an image of (H, W) pixels."""
+        return self._run(tokens_list, num_iterations, (int(image_hw[0]), int(image_hw[1])))
 
     __call__ = forward

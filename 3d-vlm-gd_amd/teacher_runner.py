@@ -12,7 +12,8 @@ PyTorch-ROCm inference).  What lives here is the glue around them:
   pair's targets in the cache layout; the reference aggregator's hard-wired `return_attn=True` is neutralised for the duration of the
   call (the selected blocks return a 1-element placeholder instead of the maps); with `fused_heads` the three dense-prediction heads run on
   the HIP kernels (teacher_heads.FusedDPTHead) instead of the user's modules, with `fused_tracker` the tracker's tail runs on
-  teacher_tracker.FusedTracker, and with `fused_patch_embed` the aggregator's DINOv2 patch embedder runs on teacher_blocks.FusedDinoEmbed;
+  teacher_tracker.FusedTracker, with `fused_patch_embed` the aggregator's DINOv2 patch embedder runs on teacher_blocks.FusedDinoEmbed, and with
+  `fused_camera_head` the camera head runs on teacher_heads.FusedCameraHead;
 * `MASt3RTeacherRunner` — `extract_mast3r_features` + `filter_and_match_keypoints` + the depth branch
   (src/finetune_timm_mast3r.py:345-469, 617-633) around the user's `dust3r.inference.inference`.
 """
@@ -103,7 +104,7 @@ class VGGTTeacherRunner:
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
     def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32,
-                 fused_updateformer=False, *, fused_patch_embed=False, fused_tracker=False):
+                 fused_updateformer=False, *, fused_patch_embed=False, fused_camera_head=False, camera_dtype=torch.float32, fused_tracker=False):
         if fused_updateformer and not fused_tracker:
             raise GdHipError("VGGTTeacherRunner: fused_updateformer=True needs fused_tracker=True (the fused update transformer runs inside FusedTracker's loop)")
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
@@ -142,6 +143,13 @@ class VGGTTeacherRunner:
                 raise GdHipError("VGGTTeacherRunner: fused_patch_embed=True: the aggregator has no `patch_embed`")
             self.embed = FusedDinoEmbed(agg.patch_embed, dtype=dtype, name="aggregator.patch_embed")
             self.embed.check_aggregator(agg)
+        # fused_camera_head (keyword only): the camera head runs on the few-row HIP kernels (teacher_heads.FusedCameraHead, weight type `camera_dtype`:
+        # torch.float32 is the faithful mode, the reference runs this head in fp32).  Independent of the other switches; a head the class refuses raises
+        # here, not in targets().
+        self.camera = None
+        if fused_camera_head:
+            from .teacher_heads import FusedCameraHead
+            self.camera = FusedCameraHead(vggt.camera_head, dtype=camera_dtype, name="camera_head")
 
     def _block_inputs(self, rgb_vggt):
         """What the aggregator hands its first frame block, produced by the aggregator itself: its forward runs as it stands (normalisation, the
@@ -194,15 +202,24 @@ class VGGTTeacherRunner:
         return tokens_list, ps_idx, qk
 
     @torch.no_grad()
+    def cameras(self, tokens_list, image_hw):
+        """-> (extrinsic [B, S, 3, 4], intrinsic [B, S, 3, 3]) of the last refinement iteration: the user's camera head then `pose_decoder` (or the lazily
+        imported one); with fused_camera_head, FusedCameraHead.poses — or, when a `pose_decoder` was given, FusedCameraHead.forward through that decoder."""
+        dec = self.pose_decoder
+        if self.camera is not None and dec is None:
+            _, extrinsic, intrinsic = self.camera.poses(tokens_list, image_hw)
+            return extrinsic, intrinsic
+        pose_enc = (self.camera if self.camera is not None else self.m.camera_head)(tokens_list)[-1]
+        if dec is None:
+            from vggt.utils.pose_enc import pose_encoding_to_extri_intri as dec       # the user's teacher package
+        return dec(pose_enc, image_hw)
+
+    @torch.no_grad()
     def targets(self, rgb_vggt, num_keypoints=300, min_distance=5, generator=None):
         """rgb_vggt [1, 2, 3, H, W] in [0, 1] -> the pair's target dict (teacher_glue.extract_vggt_targets), or None."""
         m, agg = self.m, self.m.aggregator
         tokens_list, ps_idx, qk = self.aggregate(rgb_vggt)
-        pose_enc = m.camera_head(tokens_list)[-1]
-        dec = self.pose_decoder
-        if dec is None:
-            from vggt.utils.pose_enc import pose_encoding_to_extri_intri as dec       # the user's teacher package
-        extrinsic, intrinsic = dec(pose_enc, rgb_vggt.shape[-2:])
+        extrinsic, intrinsic = self.cameras(tokens_list, rgb_vggt.shape[-2:])
         heads = self.heads
         depth_map, _ = (heads["depth_head"] if heads else m.depth_head)(tokens_list, rgb_vggt, ps_idx)
         _, point_conf = (heads["point_head"] if heads else m.point_head)(tokens_list, rgb_vggt, ps_idx)

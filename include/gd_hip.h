@@ -670,6 +670,37 @@ int gd_dino_assemble_tokens(const void* patch, int patch_dtype, const float* cls
 int gd_vggt_tokens_from_dino(const float* x, const float* gamma, const float* beta, float eps, const float* camera, const float* regs, float* tokens,
                              long* pos, int B, int S, int gh, int gw, int R, int Rg, int D, void* stream);
 
+/* The VGGT teacher's camera head (vggt/heads/camera_head.py:83-154, run in fp32 outside autocast, src/finetune_timm_vggt.py:359-366) on its M = B * S
+ * token rows (teacher_heads.FusedCameraHead; the LayerNorms between these calls are gd_layernorm_fwd).  Each entry point is one launch on `stream`,
+ * allocates nothing and refuses arguments outside its contract, naming the offending value, before any launch.
+ * gd_rows_linear: y[M, N] = epilogue(prologue(x)[M, K] . W[N, K]^T) for 1 <= M <= 8 rows; replaces the nn.Linear of camera_head.py:123/127
+ *   (embed_pose), :130 (poseLN_modulation = SiLU, Linear), vggt/layers/attention.py:89,122 (qkv, proj), vggt/layers/mlp.py (fc1, GELU, fc2) and the
+ *   LayerScale + residual add of vggt/layers/block.py:87-90,124-125.  x fp32 (row stride ldx), W fp32 | bf16 (w_dtype, row stride ldw >= K), y fp32
+ *   (row stride ldy), fp32 accumulation.  prologue: 0 none, 1 SiLU(x).  Epilogue in this order: + bias[N] (nullable); activation 0 none, 1 exact-erf
+ *   GELU; if residual (row stride ldr) is given y = residual + gamma[n] * v, gamma nullable = 1.  y may be residual itself (same pointer and
+ *   stride: in place on the token stream); it may overlap neither x nor W.  Limits, refused not rerouted: K % 4 == 0 (fp32 W) or K % 8 == 0 (bf16 W,
+ *   then ldw % 8 == 0 too); M * K <= 16384 (x is staged once per workgroup in 64 KB of LDS: M <= 8 at K <= 2048, M <= 2 at K <= 8192); ldx, ldy,
+ *   ldr, ldw multiples of 4; x, W, y, residual 16-byte aligned.  W streams once from global memory to registers; one wave sums each output element
+ *   in an order fixed by K and w_dtype alone (no split-K, no atomics): row m of an M-row call is bit-identical to the same row computed alone, a
+ *   column is bit-identical whatever N and the grid are.
+ * gd_rows_attention: vggt/layers/attention.py:87-123 with rope = None and qk_norm = False, between qkv and proj: qkv fp32 [B * S, 3 * H * hd] (row
+ *   stride ld; q | k | v, head-major), o fp32 [B * S, H * hd] (row stride ldo) = softmax(scale q k^T) v per (b, head) over that entry's S rows
+ *   only, no mask, exact fp32 with the maximum subtracted.  1 <= S <= 8; hd % 4 == 0, 4 <= hd <= 256.
+ * gd_adaln_modulate: camera_head.py:130-134, out[m, :] = gate * (LN0(x[m, :]) * (1 + scale) + shift) + x[m, :] with mod [M, 3 D] (row stride ldm)
+ *   = shift | scale | gate and LN0 a LayerNorm without affine parameters (eps given).  D % 4 == 0, D <= 8192.  out may be x itself.
+ * gd_pose_update: camera_head.py:140-152 + vggt/heads/head_act.py:12-58, and when extrinsic / intrinsic are given (both or neither, with the image
+ *   size H, W) vggt/utils/pose_enc.py:108-126 + vggt/utils/rotation.py:14-44.  raw [M, 12] holds the un-activated encoding, columns 9..11 held at
+ *   0 (embed_pose's left operand padded to K = 12): raw[:, :9] = (first ? 0 : raw[:, :9]) + delta[M, 9] (row stride ldd); enc [M, 9] =
+ *   activation(raw) per group, translation [:3], quaternion [3:7], field of view [7:9] (codes 0 linear, 1 inv_log, 2 exp, 3 relu);
+ *   extrinsic [M, 3, 4] = [quat_to_mat(enc[3:7]) | enc[:3]] (scalar-last quaternion, scaled by 2 / |q|^2); intrinsic [M, 3, 3] with
+ *   fy = (H / 2) / tan(fov_h / 2), fx = (W / 2) / tan(fov_w / 2), cx = W / 2, cy = H / 2.  A field of view of exactly 0 gives +inf, never NaN. */
+int gd_rows_linear(const float* x, const void* w, int w_dtype, float* y, int M, int N, int K, long ldx, long ldw, long ldy, const float* bias,
+                   const float* residual, long ldr, const float* gamma, int prologue, int activation, void* stream);
+int gd_rows_attention(const float* qkv, float* o, int B, int S, int H, int head_dim, long ld, long ldo, float scale, void* stream);
+int gd_adaln_modulate(const float* x, const float* mod, float* out, int M, int D, long ldx, long ldm, long ldo, float eps, void* stream);
+int gd_pose_update(const float* delta, long ldd, float* raw, float* enc, float* extrinsic, float* intrinsic, int M, int first, int trans_act,
+                   int quat_act, int fl_act, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

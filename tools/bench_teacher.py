@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer,patch_embed,patch_embed_share]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer,patch_embed,patch_embed_share,camera_head,camera_head_share]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -46,6 +46,14 @@
    tests/dino_layout.py (f32, and under bf16 autocast), alternating, each path twice; the agreement of every path with the f32 module.
    "vggt_patch_embed_share" (--sections patch_embed_share): the teacher of tracker_share built around that embedder instead of the stub convolution, everything
    else fused: the embedder alone, `aggregate` and `targets()` with fused_patch_embed off and on.
+10. "vggt_camera_head" (--sections camera_head): the camera head alone at teacher size — dim_in 2048, 4 trunk blocks, 16 heads (head dimension 128), B = 1,
+   S = 2 camera rows, 4 iterations: teacher_heads.FusedCameraHead with fp32 and with bf16 weights against the torch module of tests/camera_layout.py in
+   fp32 (as the reference runs it, outside autocast), alternating, each path twice; launches and weight bytes per call, the fused call's achieved TB/s; and
+   gd_rows_linear alone at the head's five shapes (M = 2) against gd_gemm_nt on the same operands, interleaved, three rounds, every call on another copy
+   of the weights (a pool above 512 MB, so that no call finds its weights in the 256 MB last-level cache — as in the head, which cycles through 864 MB),
+   also as a fraction of the bandwidth gd_cost_volume_teacher_stats reaches on a stream of the same size.
+   "vggt_camera_head_share" (--sections camera_head_share): the teacher of tracker_share with that camera head in place of the stub, every other switch
+   fused, with fused_camera_head off and on: the head's time, targets(), and the head's share of it.
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -130,12 +138,17 @@ def main():
         patch_embed_section(res, a, dev)
     if "patch_embed_share" in sections:
         patch_embed_share_section(res, a, dev)
+    if "camera_head" in sections:
+        camera_head_section(res, a, dev)
+    if "camera_head_share" in sections:
+        camera_head_share_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
            "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
            "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"],
-           "updateformer": ["vggt_updateformer"], "patch_embed": ["vggt_patch_embed"], "patch_embed_share": ["vggt_patch_embed_share"]}
+           "updateformer": ["vggt_updateformer"], "patch_embed": ["vggt_patch_embed"], "patch_embed_share": ["vggt_patch_embed_share"],
+           "camera_head": ["vggt_camera_head"], "camera_head_share": ["vggt_camera_head_share"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -429,6 +442,136 @@ def patch_embed_share_section(res, a, dev):
     out["speedup_aggregate"] = round(out["module_patch_embed"]["aggregate"]["median_ms"] / out["fused_patch_embed"]["aggregate"]["median_ms"], 3)
     out["speedup_targets"] = round(out["module_patch_embed"]["targets"]["median_ms"] / out["fused_patch_embed"]["targets"]["median_ms"], 3)
     res["vggt_patch_embed_share"] = out
+
+
+CAMERA = dict(dim_in=2048, trunk_depth=4, num_heads=16)
+CAMERA_SHAPES = [(2048, 6144), (2048, 2048), (2048, 8192), (8192, 2048), (2048, 1024)]          # (K, N): qkv / modulation, proj, fc1, fc2, pose_branch.fc1
+
+
+def camera_head_at_teacher_size(dev, dim_in=CAMERA["dim_in"]):
+    """The layout's camera head with torch's default initialisation, the pose branch conditioned as tests/camera_layout.fill_head does (a unit
+    quaternion part and fields of view inside (0, pi) in every iteration), LayerScale and the empty pose token away from their zero-ish defaults."""
+    import camera_layout as CAM
+    with torch.device(dev):
+        m = CAM.CameraHeadLayout(**dict(CAMERA, dim_in=dim_in)).eval()
+    with torch.no_grad():
+        for b in m.trunk:
+            torch.nn.init.constant_(b.ls1.gamma, 0.2)
+            torch.nn.init.constant_(b.ls2.gamma, 0.2)
+        torch.nn.init.normal_(m.empty_pose_tokens, std=0.5)
+        m.pose_branch.fc2.weight.mul_(0.1)
+        m.pose_branch.fc2.bias[6] += 1.0
+        m.pose_branch.fc2.bias[7:] += 0.4
+    return m
+
+
+def camera_head_section(res, a, dev):
+    from gd_amd.teacher_heads import FusedCameraHead
+    m = camera_head_at_teacher_size(dev)
+    D, S, iters = CAMERA["dim_in"], 2, 4
+    toks = [torch.randn(1, S, 1 + 4 + 37 * 37, D, device=dev)]
+    f32, b16 = FusedCameraHead(m, dtype=torch.float32), FusedCameraHead(m, dtype=torch.bfloat16)
+
+    def module():
+        with torch.no_grad():
+            return m(toks)
+    want = module()[-1]
+    out = dict(CAMERA, B=1, S=S, iterations=iters, max_abs_last_encoding={"scale": float(want.abs().max()), "fused_f32": T.max_abs(f32.forward(toks)[-1], want),
+                                                                          "fused_bf16_weights": T.max_abs(b16.forward(toks)[-1], want)})
+    for f, tag in ((f32, "fused_f32"), (b16, "fused_bf16_weights")):
+        f.launches = 0
+        f.forward(toks)
+        out[f"launches_per_call_{tag}"] = f.launches
+        out[f"weight_bytes_per_call_{tag}"] = f.weight_bytes * iters
+    # the module's launches, counted as the aten operators one forward dispatches that are not views (each is at least one kernel)
+    from torch.utils._python_dispatch import TorchDispatchMode
+    views = ("view", "reshape", "permute", "transpose", "expand", "unbind", "chunk", "split", "select", "slice", "detach", "squeeze", "alias", "aten.t.")
+
+    class Count(TorchDispatchMode):
+        n = 0
+
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            Count.n += not any(v in str(func) for v in views)
+            return func(*args, **(kwargs or {}))
+    with Count():
+        module()
+    out["launches_per_call_module_f32"] = int(Count.n)
+    paths = (("module_f32", module), ("fused_f32", lambda: f32.forward(toks)), ("fused_bf16_weights", lambda: b16.forward(toks)))
+    for suffix in ("", "_again"):
+        for name, fn in paths:
+            out[name + suffix] = timed(fn, a.warm, a.iters)
+    best = lambda n: min(out[n]["median_ms"], out[n + "_again"]["median_ms"])
+    for tag in ("fused_f32", "fused_bf16_weights"):
+        out[f"speedup_{tag}_vs_module_f32"] = round(best("module_f32") / best(tag), 3)
+        out[f"achieved_TBs_{tag}"] = round(out[f"weight_bytes_per_call_{tag}"] / (best(tag) * 1e-3) / 1e12, 3)
+        out[f"fraction_of_peak_HBM_{tag}"] = round(out[f"achieved_TBs_{tag}"] / HBM_TBS, 3)
+    del f32, b16, m
+    torch.cuda.empty_cache()
+    # gd_rows_linear alone against gd_gemm_nt, M = 2, interleaved, three rounds; every call streams another copy of the weights
+    shapes = {}
+    for K, N in CAMERA_SHAPES:
+        nbytes = N * K * 4
+        copies = max(3, -(-(512 << 20) // nbytes))
+        pool = [torch.randn(N, K, device=dev) * K ** -0.5 for _ in range(copies)]
+        x, bias = torch.randn(2, K, device=dev), torch.randn(N, device=dev)
+        y = torch.empty(2, N, device=dev)
+        hw = 1024
+        P = max(1, round(nbytes / (2 * hw * hw * 4)))
+        maps = [(torch.rand(P, hw, hw, device=dev), torch.rand(P, hw, hw, device=dev)) for _ in range(max(3, -(-(512 << 20) // (2 * P * hw * hw * 4))))]
+        L, st = _lib.lib(), _lib.stream()
+        rl_args = [(x.data_ptr(), w.data_ptr(), _lib.F32, y.data_ptr(), 2, N, K, K, K, N, bias.data_ptr(), None, 0, None, 0, 0, st) for w in pool]
+        tstats = torch.empty(P, 2, hw, 4, device=dev)
+        ts_args = [(t1.data_ptr(), t2.data_ptr(), P, hw, hw, tstats.data_ptr(), st) for t1, t2 in maps]
+        assert L.gd_rows_linear(*rl_args[0]) == 0 and L.gd_cost_volume_teacher_stats(*ts_args[0]) == 0
+        state = {"i": 0}
+
+        def nxt(lst):
+            state["i"] = (state["i"] + 1) % len(lst)
+            return lst[state["i"]]
+        entry = {"K": K, "N": N, "weight_MB": round(nbytes / 2 ** 20, 1), "weight_copies": copies, "stream_MB": round(2 * P * hw * hw * 4 / 2 ** 20, 1), "rounds": []}
+        for _ in range(3):
+            # the two streaming kernels run 10 to 20 us: they are called at the C ABI with prepared arguments (as FusedCameraHead calls them), the
+            # tensor wrappers' checks alone cost about as much on the host; gd_gemm_nt goes through its wrapper
+            r = {"rows_linear": timed(lambda: L.gd_rows_linear(*nxt(rl_args)), a.warm, a.iters, reps=copies),
+                 "gemm_nt": timed(lambda: ops.gemm_nt(x, nxt(pool), out=y, bias=bias), a.warm, a.iters, reps=copies),
+                 "teacher_stats_stream": timed(lambda: L.gd_cost_volume_teacher_stats(*nxt(ts_args)), a.warm, a.iters, reps=len(maps))}
+            entry["rounds"].append(r)
+        med = lambda k: sorted(r[k]["median_ms"] for r in entry["rounds"])
+        rl, gm, ts = med("rows_linear"), med("gemm_nt"), med("teacher_stats_stream")
+        entry["rows_linear_ms"], entry["gemm_nt_ms"] = rl, gm
+        entry["faster_beyond_the_spread"] = bool(rl[-1] < gm[0])                # the slowest rows_linear round against the fastest gemm_nt round
+        entry["speedup_vs_gemm_nt"] = round(gm[1] / rl[1], 2)
+        entry["rows_linear_TBs"] = round(nbytes / (rl[1] * 1e-3) / 1e12, 3)
+        entry["teacher_stats_TBs"] = round(2 * P * hw * hw * 4 / (ts[1] * 1e-3) / 1e12, 3)
+        entry["fraction_of_teacher_stats_bandwidth"] = round(entry["rows_linear_TBs"] / entry["teacher_stats_TBs"], 3)
+        shapes[f"{K}->{N}"] = entry
+        del pool, maps
+        torch.cuda.empty_cache()
+    out["rows_linear_M2"] = shapes
+    res["vggt_camera_head"] = out
+
+
+def camera_head_share_section(res, a, dev):
+    """The camera head's share of `targets()`: the VGGT-shaped teacher of tracker_share with a real camera head, every other switch fused (patch
+    embedder excepted: that teacher has the stub convolution), with fused_camera_head off and on."""
+    import camera_layout as CAM
+    teacher, track, img = vggt_shaped_teacher(a, dev)
+    head = camera_head_at_teacher_size(dev, 2 * a.width)
+    teacher.camera_head = head
+    out = dict(CAMERA, dim_in=2 * a.width, width=a.width, depth=a.depth, aggregator="fused_blocks bf16", heads="fused_heads f32",
+               tracker="fused_tracker + fused_updateformer")
+    for tag, on in (("module_camera_head", False), ("fused_camera_head", True)):
+        r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=None if on else CAM.decode_pose, fused_blocks=True, fused_heads=True,
+                              fused_updateformer=True, fused_camera_head=on, fused_tracker=True)
+        toks, _, _ = r.aggregate(img)
+        got = r.targets(img)
+        out[tag] = {"cameras": timed(lambda: r.cameras(toks, img.shape[-2:]), a.warm, a.iters), "targets": timed(lambda: r.targets(img), 1, min(a.iters, 3)),
+                    "targets_returned_none": got is None, "keypoints": 0 if got is None else int(got["kp_1"].shape[0]), "token_dtype": str(toks[-1].dtype)}
+        out[tag]["camera_share_of_targets"] = round(out[tag]["cameras"]["median_ms"] / out[tag]["targets"]["median_ms"], 3)
+        del r
+    out["speedup_cameras"] = round(out["module_camera_head"]["cameras"]["median_ms"] / out["fused_camera_head"]["cameras"]["median_ms"], 3)
+    out["speedup_targets"] = round(out["module_camera_head"]["targets"]["median_ms"] / out["fused_camera_head"]["targets"]["median_ms"], 3)
+    res["vggt_camera_head_share"] = out
 
 
 def updateformer_section(res, a, dev):
