@@ -207,6 +207,8 @@ SIGNATURES = {
     "gd_rows_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_long, c_float, c_void_p]),
     "gd_adaln_modulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_long, c_float, c_void_p]),
     "gd_pose_update": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gd_tokens_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_void_p, c_int, c_void_p, c_long, c_int,
+                                 c_void_p]),
 }
 
 

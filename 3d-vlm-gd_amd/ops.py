@@ -1901,3 +1901,36 @@ def pose_update(delta, raw, first, acts=("linear", "linear", "relu"), image_hw=N
         K = torch.empty(M, 3, 3, dtype=torch.float32, device=delta.device)
     check(lib().gd_pose_update(ptr(delta), ldd, ptr(raw), ptr(enc), ptr(E), ptr(K), M, int(bool(first)), *codes, H, W, stream()), "gd_pose_update")
     return enc if image_hw is None else (enc, E, K)
+
+
+# ------------------------------------------------------------------------------------------------ small-tile fp32 linear (csrc/tokens_linear.hip)
+def tokens_linear(x, w, bias=None, *, out=None, residual=None, gelu=False, accumulate=False):
+    """x [M, K] fp32, w [N, K] fp32 (rows of both may be strided; K a multiple of 4) -> y [M, N] fp32 = epilogue(x w^T) on exact f32 MFMA products
+    (gd_tokens_linear: 32 x 32 / 64 x 32 tiles whose four waves split K — the linear for tens to a couple of thousand token rows, where
+    gemm_nt's 128 x 128 tiles leave most of the device idle).  Epilogue in gemm_nt's order: + bias [N], exact GELU with gelu=True, + residual
+    [M, N], + out with accumulate=True (which needs out=).  out= a view to write (default: a new tensor whose rows are padded to a multiple of 4);
+    out may be `residual` itself (in place), never x or w.  Honours set_gemm_profiler like gemm_nt; the record's epilogue tag starts with "t" ("tbra0+"), which tells the two kernels apart in by_shape()."""
+    ldx = _f32rows(x, "tokens_linear: x")
+    M, K = x.shape
+    ldw = _f32rows(w, "tokens_linear: w", K)
+    N = w.shape[0]
+    _req(not accumulate or out is not None, "tokens_linear: accumulate=True adds onto out=, which is missing")
+    y = torch.empty(M, N + (-N) % 4, dtype=torch.float32, device=x.device)[:, :N] if out is None else out
+    ldy = _f32rows(y, "tokens_linear: out", N)
+    _req(y.shape[0] == M, f"tokens_linear: out has {y.shape[0]} rows, x has {M}")
+    ldr = 0
+    if residual is not None:
+        ldr = _f32rows(residual, "tokens_linear: residual", N)
+        _req(residual.shape[0] == M, f"tokens_linear: residual has {residual.shape[0]} rows, x has {M}")
+    _req(bias is None or (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (N,)),
+         f"tokens_linear: bias must be a contiguous CUDA fp32 [{N}]")
+    if _PROFILER is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib().gd_tokens_linear(ptr(x), ptr(w), ptr(y), M, N, K, ldx, ldw, ldy, ptr(bias), int(bool(gelu)), ptr(residual), ldr, int(bool(accumulate)), stream())
+    if _PROFILER is not None:
+        e1.record()
+        tag = "t" + ("b" if bias is not None else "") + ("r" if residual is not None else "")
+        _PROFILER.records.append((e0, e1, 2.0 * M * N * K, (M, N, K, 1, f"{tag}a{int(bool(gelu))}{'+' if accumulate else ''}", "float32", "float32")))
+    check(rc, "gd_tokens_linear")
+    return y

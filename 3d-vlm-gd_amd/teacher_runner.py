@@ -104,9 +104,13 @@ class VGGTTeacherRunner:
     = vggt.utils.pose_enc.pose_encoding_to_extri_intri of the user's vggt package (imported lazily when not given)."""
 
     def __init__(self, vggt, dtype=torch.bfloat16, prefix=5, pose_decoder=None, fused_blocks=False, fused_heads=False, heads_dtype=torch.float32,
-                 fused_updateformer=False, *, fused_patch_embed=False, fused_camera_head=False, camera_dtype=torch.float32, fused_tracker=False):
+                 fused_updateformer=False, *, fused_patch_embed=False, fused_camera_head=False, camera_dtype=torch.float32, tracker_linear="gemm_nt",
+                 fused_tracker=False):
         if fused_updateformer and not fused_tracker:
             raise GdHipError("VGGTTeacherRunner: fused_updateformer=True needs fused_tracker=True (the fused update transformer runs inside FusedTracker's loop)")
+        if tracker_linear != "gemm_nt" and not fused_tracker:
+            raise GdHipError(f"VGGTTeacherRunner: tracker_linear={tracker_linear!r} needs fused_tracker=True (it chooses the linear kernel of FusedTracker and its "
+                             f"FusedUpdateFormer)")
         self.m, self.dtype, self.prefix, self.pose_decoder = vggt, dtype, prefix, pose_decoder
         agg = vggt.aggregator
         per = getattr(agg, "aa_block_size", 1)
@@ -127,12 +131,13 @@ class VGGTTeacherRunner:
         # fused_tracker: the tracker's correlation pyramid, window sampling, position embedding, glue and small MLPs run on the HIP kernels
         # (teacher_tracker.FusedTracker, fp32; the update transformer stays the user's module unless fused_updateformer, off by default, hands it to
         # teacher_tracker.FusedUpdateFormer; pass both by keyword, fused_tracker stays the last one — keyword only since fused_patch_embed, which is keyword only,
-        # stands in front of it).  Independent of fused_blocks and fused_heads; a tracker the
-        # class refuses raises here, not in targets().
+        # stands in front of it).  tracker_linear (keyword only, "gemm_nt" by default): "tokens" runs the linear layers of the fused tracker and of its
+        # fused update transformer on gd_tokens_linear, the small-tile fp32 kernel for their few hundred rows.  Independent of fused_blocks and
+        # fused_heads; a tracker the class refuses raises here, not in targets().
         self.tracker = None
         if fused_tracker:
             from .teacher_tracker import FusedTracker
-            self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker", fused_updateformer=fused_updateformer)
+            self.tracker = FusedTracker(vggt.track_head.tracker, name="track_head.tracker", fused_updateformer=fused_updateformer, linear=tracker_linear)
 
         # fused_patch_embed (keyword only): the aggregator's DINOv2 patch embedder runs on the HIP kernels (teacher_blocks.FusedDinoEmbed, operand type
         # `dtype`).  Independent of the other switches; an embedder, or an aggregator around it, that the class refuses raises here, not in targets().

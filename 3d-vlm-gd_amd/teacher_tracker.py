@@ -63,6 +63,23 @@ def _lin_bias(b, n, like):
     return b.detach().float().contiguous() if b is not None else torch.zeros(n, dtype=torch.float32, device=like.device)
 
 
+LINEAR_KINDS = ("gemm_nt", "tokens")
+
+
+def _linear_kind(linear, who):
+    if linear not in LINEAR_KINDS:
+        raise GdHipError(f"{who}: linear = {linear!r}: 'gemm_nt' (gd_gemm_nt, the default) or 'tokens' (gd_tokens_linear) are served")
+    return linear
+
+
+def _linear(kind, a, w, bias, act=0, residual=None, out=None, accumulate=False):
+    """One fp32 linear layer of the tracker on gd_gemm_nt or, with kind "tokens", on gd_tokens_linear (the small-tile kernel for these row counts);
+    act: 0 none, 1 exact GELU."""
+    if kind == "tokens":
+        return ops.tokens_linear(a, w, bias, out=out, residual=residual, gelu=act == 1, accumulate=accumulate)
+    return ops.gemm_nt(a, w, out, bias=bias, act=act, residual=residual, accumulate=accumulate)
+
+
 class FusedUpdateFormer:
     """FusedUpdateFormer(updateformer)(x [B, N, S, 3C + 4]) -> (delta [B, N, S, C + 2], None): the tracker's update transformer
     (vggt/heads/track_modules/blocks.py:19-144 EfficientUpdateFormer on modules.py:147-218 AttnBlock / CrossAttnBlock) on gd_layernorm_fwd, gd_gemm_nt
@@ -80,10 +97,14 @@ class FusedUpdateFormer:
     cross block.  The blocks whose point rows are the last ones written add them onto the saved input tokens (the GEMM's accumulate), so
     `tokens[:, :N] + init_tokens` costs no pass of its own; a last time block without a space stage runs on the point rows alone.
 
+    linear="tokens" (off by default) sends every linear layer through gd_tokens_linear instead of gd_gemm_nt: the same products in exact fp32 on
+    32 x 32 tiles whose four waves split K, for the few hundred rows this transformer sees.
+
     Read once, duck-typed on the attribute names; what the kernels do not serve is refused here, naming the attribute."""
 
-    def __init__(self, former, name="updateformer"):
+    def __init__(self, former, name="updateformer", *, linear="gemm_nt"):
         self.name = name
+        self.linear = _linear_kind(linear, f"FusedUpdateFormer: {name}")
 
         def fail(attr, why):
             raise GdHipError(f"FusedUpdateFormer: {name}.{attr}: {why}")
@@ -203,7 +224,7 @@ class FusedUpdateFormer:
 
     def _gemm(self, a, p, **kw):
         self.launches += 1
-        return ops.gemm_nt(a, p[0], bias=p[1], **kw)
+        return _linear(self.linear, a, p[0], p[1], **kw)
 
     def _attend(self, q, k, v, seq_q, seq_k, H):
         """q [rows_q, >= D], k, v [rows_k, >= D] (column blocks; equal row strides within each) under their sequence layouts -> o [rows_q, D]."""
@@ -307,10 +328,12 @@ class FusedTracker:
     a 16-bit mode is not offered).  The parameters are read and packed once, here, on whatever device the module is on (build it after loading the
     checkpoint); if that is not the device of the feature map handed to `begin` / `forward`, the packed copies are moved there on that call (`_to`).
     The user's `updateformer` is called as it stands and must itself live on the feature map's device; fused_updateformer=True (off by default) runs
-    it as a FusedUpdateFormer instead, read and refused here like everything else."""
+    it as a FusedUpdateFormer instead, read and refused here like everything else.  linear="tokens" (off by default) runs the tracker's own linear
+    layers (corr_mlp, ffeat_updater, the predictors) on gd_tokens_linear instead of gd_gemm_nt and hands the choice to the FusedUpdateFormer."""
 
-    def __init__(self, tracker, name="tracker", fused_updateformer=False):
+    def __init__(self, tracker, name="tracker", fused_updateformer=False, *, linear="gemm_nt"):
         self.name = name
+        self.linear = _linear_kind(linear, f"FusedTracker: {name}")
 
         def fail(attr, why):
             raise GdHipError(f"FusedTracker: {name}.{attr}: {why}")
@@ -365,7 +388,7 @@ class FusedTracker:
         self.ffeat_updater = (f32(mods[0].weight), self._bias(mods[0]))
         self.updateformer = need(tracker, "updateformer")
         if fused_updateformer:
-            self.updateformer = FusedUpdateFormer(self.updateformer, name=f"{name}.updateformer")
+            self.updateformer = FusedUpdateFormer(self.updateformer, name=f"{name}.updateformer", linear=linear)
             if self.updateformer.Din != self.D or self.updateformer.Dout != C + 2:
                 fail("updateformer", f"maps {self.updateformer.Din} -> {self.updateformer.Dout}, not {self.D} -> {C + 2}")
         qrt = need(tracker, "query_ref_token")
@@ -478,7 +501,7 @@ class FusedTracker:
         corr = ops.corr_sample(st.pyramid, st.feats, st.coords, self.radius, ld=self.kpad)
         st.corr = corr
         w1, b1, w2, b2 = self.corr_mlp
-        c = ops.gemm_nt(ops.gemm_nt(corr.view(M, self.kpad), w1, bias=b1, act=1), w2, bias=b2)
+        c = _linear(self.linear, _linear(self.linear, corr.view(M, self.kpad), w1, b1, act=1), w2, b2)
         x = ops.track_assemble(st.coords, c.view(B, S, N, C), st.feats, st.pos, self.qrt, self.max_scale)
         delta = self.updateformer(x)
         delta = delta[0] if isinstance(delta, (tuple, list)) else delta
@@ -488,14 +511,14 @@ class FusedTracker:
         g, b, eps = self.ffeat_norm
         y = ops.layernorm_fwd(dfeat, g, b, eps, save_stats=False)[0]
         wu, bu = self.ffeat_updater
-        st.feats = ops.gemm_nt(y, wu, bias=bu, act=1, residual=st.feats.view(M, C)).view(B, N, S, C)
+        st.feats = _linear(self.linear, y, wu, bu, act=1, residual=st.feats.view(M, C)).view(B, N, S, C)
         return pred
 
     @torch.no_grad()
     def finish(self, st, apply_sigmoid=True):
         """-> (vis [B, S, N], conf [B, S, N] or None) (base_track_predictor.py:194-204)."""
         B, S, N, C = st.B, st.S, st.N, self.C
-        o = ops.gemm_nt(st.feats.view(B * N * S, C), self.predictors[0], bias=self.predictors[1]).view(B, N, S, 8)
+        o = _linear(self.linear, st.feats.view(B * N * S, C), self.predictors[0], self.predictors[1]).view(B, N, S, 8)
         vis = o[..., 0].permute(0, 2, 1)
         conf = o[..., 1].permute(0, 2, 1) if self.predict_conf else None
         if apply_sigmoid:

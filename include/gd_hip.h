@@ -701,6 +701,21 @@ int gd_adaln_modulate(const float* x, const float* mod, float* out, int M, int D
 int gd_pose_update(const float* delta, long ldd, float* raw, float* enc, float* extrinsic, float* intrinsic, int M, int first, int trans_act,
                    int quat_act, int fl_act, int H, int W, void* stream);
 
+/* gd_tokens_linear: y[M, N] = epilogue(x[M, K] . W[N, K]^T), fp32 operands and result, exact f32 MFMA products (no 16-bit operand mode), for the
+ *   token counts between gd_rows_linear (M <= 8) and gd_gemm_nt's 128 x 128 tiles: the nn.Linear layers of the VGGT tracker's update transformer
+ *   (vggt/heads/track_modules/blocks.py:19-144, modules.py:147-218: M = B (N + nv) S or B N S rows, a few hundred columns) and the tracker's own
+ *   corr_mlp / ffeat_updater / predictors (base_track_predictor.py:60-80), teacher_tracker.FusedUpdateFormer / FusedTracker (linear="tokens").
+ *   x (row stride ldx), W (row stride ldw) K-contiguous as in nn.Linear, y row stride ldy.  Epilogue in gd_gemm_nt's order: + bias[N] (nullable);
+ *   exact-erf GELU when gelu = 1; + residual[M, N] (nullable, row stride ldr); + y when accumulate = 1.  One launch on `stream`, no workspace.
+ *   A workgroup of four waves owns one 32 x 32 (or 64 x 32) output tile; the waves split K by 16-k steps (wave p: steps p, p + 4, ...) and their
+ *   partial tiles are added in the order (p0 + p1) + p2 + p3: the summation order of an element depends on K alone — a row block of an M-row call, a
+ *   column block of an N-column call, another stride, another run and the in-place call give the same bits.
+ *   Refused before any launch, naming the argument: null x / W / y; M, N < 1; K < 4 or K % 4 != 0; ldx, ldw < K or ldy, ldr < N or any of them not
+ *   a multiple of 4; x, W, y, bias or residual not 16-byte aligned; y overlapping x or W; y overlapping residual without being the same pointer and
+ *   stride (y == residual: in place on the token stream).  Rows >= M, columns >= N and the padding between N and ldy are never read or written. */
+int gd_tokens_linear(const float* x, const float* w, float* y, int M, int N, int K, long ldx, long ldw, long ldy, const float* bias, int gelu,
+                     const float* residual, long ldr, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

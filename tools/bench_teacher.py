@@ -1,6 +1,6 @@
 """Teacher block-stack timings on one GPU, VGGT and MASt3R (not the training benchmark: bench.py stays the yardstick of the step).
 
-  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer,patch_embed,patch_embed_share,camera_head,camera_head_share]
+  python3 tools/bench_teacher.py [--out profiles/bench_teacher.json] [--iters 5] [--warm 2] [--depth 24] [--sections vggt,mast3r,heads,heads_share,mast3r_heads,mast3r_heads_share,tracker,tracker_share,updateformer,patch_embed,patch_embed_share,camera_head,camera_head_share,tokens_linear]
 
 1. The aggregator's block stack at VGGT-1B size — width 1024, 16 heads, 24 frame + 24 global blocks, S = 2 views of P = 1374 tokens
    (518^2 at patch 14 + 5 prefix tokens), random weights, bf16: `VGGTTeacherRunner.aggregate` with fused_blocks (the HIP kernels,
@@ -54,6 +54,11 @@
    also as a fraction of the bandwidth gd_cost_volume_teacher_stats reaches on a stream of the same size.
    "vggt_camera_head_share" (--sections camera_head_share): the teacher of tracker_share with that camera head in place of the stub, every other switch
    fused, with fused_camera_head off and on: the head's time, targets(), and the head's share of it.
+11. "tokens_linear" (--sections tokens_linear): gd_tokens_linear against gd_gemm_nt on the same operands, alternating in one run, each with its epilogue
+   (+ bias, + residual), device events around 20 back-to-back calls (the new kernel through its C entry point, so that the host keeps ahead of it): the update transformer's products — M in {728, 600, 128} x (K, N) in {(384, 1152),
+   (384, 768), (384, 384), (384, 1536), (1536, 384), (388, 384), (384, 132)} — and the tracker's own three at M = 600: microseconds, TFLOP/s and the ratio to
+   the f32 MFMA floor 2 M N K / 157.3 TFLOP/s.  "vggt_updateformer" also times FusedUpdateFormer(linear="tokens") ("fused_tokens") with its launches and its
+   per-kernel split; "vggt_tracker" and "vggt_tracker_share_of_targets" also run FusedTracker / the runner with the transformer fused on "tokens".
 Prints one JSON object (also written to --out; sections that were not run keep what the file held)."""
 import argparse
 import hashlib
@@ -142,13 +147,15 @@ def main():
         camera_head_section(res, a, dev)
     if "camera_head_share" in sections:
         camera_head_share_section(res, a, dev)
+    if "tokens_linear" in sections:
+        tokens_linear_section(res, a, dev)
     # every section that ran in this call carries the library it ran on; sections that were not run keep what the file held
     lib_hash = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     ran = {"vggt": ["block_stack", "fused_kernels_at_vggt_size", "qk_norm_rope_bandwidth"], "mast3r": ["mast3r_block_stack", "cross_attention_kernel"],
            "heads": ["vggt_dpt_heads"], "heads_share": ["vggt_dpt_heads_share_of_targets"], "mast3r_heads": ["mast3r_heads"],
            "mast3r_heads_share": ["mast3r_heads_share"], "tracker": ["vggt_tracker"], "tracker_share": ["vggt_tracker_share_of_targets"],
            "updateformer": ["vggt_updateformer"], "patch_embed": ["vggt_patch_embed"], "patch_embed_share": ["vggt_patch_embed_share"],
-           "camera_head": ["vggt_camera_head"], "camera_head_share": ["vggt_camera_head_share"]}
+           "camera_head": ["vggt_camera_head"], "camera_head_share": ["vggt_camera_head_share"], "tokens_linear": ["tokens_linear"]}
     for sec in sections:
         for key in ran.get(sec, []):
             if key in res:
@@ -268,6 +275,7 @@ def tracker_section(res, a, dev):
     cached = teacher_size_tracker(dev, cache_pos_embed=True)
     cached.load_state_dict(trk.state_dict())
     fused, fused_uf = FusedTracker(trk), FusedTracker(trk, fused_updateformer=True)
+    fused_tok = FusedTracker(trk, fused_updateformer=True, linear="tokens")
     fmaps = torch.randn(1, S, 128, H, W, device=dev)
     cl = fmaps.permute(0, 1, 3, 4, 2).contiguous()
     q = torch.rand(1, N, 2, device=dev) * torch.tensor([2.0 * (W - 1), 2.0 * (H - 1)], device=dev)
@@ -282,8 +290,13 @@ def tracker_section(res, a, dev):
     out["module_host_table"] = timed(lambda: module_run(trk), 1, min(a.iters, 3))
     for name, fn in (("module_cached_table", lambda: module_run(cached)), ("fused", lambda: fused(q, fmaps, iters=iters)),
                      ("fused_channel_last", lambda: fused(q, iters=iters, fmaps_cl=cl)), ("fused_updateformer", lambda: fused_uf(q, fmaps, iters=iters)),
-                     ("fused_again", lambda: fused(q, fmaps, iters=iters)), ("fused_updateformer_again", lambda: fused_uf(q, fmaps, iters=iters))):
+                     ("fused_updateformer_tokens", lambda: fused_tok(q, fmaps, iters=iters)),
+                     ("fused_again", lambda: fused(q, fmaps, iters=iters)), ("fused_updateformer_again", lambda: fused_uf(q, fmaps, iters=iters)),
+                     ("fused_updateformer_tokens_again", lambda: fused_tok(q, fmaps, iters=iters))):
         out[name] = timed(fn, a.warm, a.iters)
+    out["fused_updateformer_tokens_vs_module_final_coords_max_abs_px"] = float((want - fused_tok(q, fmaps, iters=iters)[0][-1]).abs().max())
+    out["speedup_fused_updateformer_tokens_vs_fused"] = round(min(out["fused"]["median_ms"], out["fused_again"]["median_ms"]) /
+                                                              min(out["fused_updateformer_tokens"]["median_ms"], out["fused_updateformer_tokens_again"]["median_ms"]), 3)
     out["fused_updateformer_vs_module_final_coords_max_abs_px"] = float((want - fused_uf(q, fmaps, iters=iters)[0][-1]).abs().max())
     out["speedup_fused_updateformer_vs_fused"] = round(min(out["fused"]["median_ms"], out["fused_again"]["median_ms"]) /
                                                        min(out["fused_updateformer"]["median_ms"], out["fused_updateformer_again"]["median_ms"]), 3)
@@ -340,9 +353,11 @@ def tracker_share_section(res, a, dev):
     C = a.width
     teacher, track, img = vggt_shaped_teacher(a, dev)
     out = dict(TRACKER, width=C, depth=a.depth, aggregator="fused_blocks bf16", heads="fused_heads f32")
-    for tag, on, uf in (("module_tracker", False, False), ("fused_tracker", True, False), ("fused_tracker_fused_updateformer", True, True)):
+    for tag, on, uf, lin in (("module_tracker", False, False, "gemm_nt"), ("fused_tracker", True, False, "gemm_nt"),
+                             ("fused_tracker_fused_updateformer", True, True, "gemm_nt"), ("fused_tracker_fused_updateformer_tokens", True, True, "tokens"),
+                             ("fused_tracker_again", True, False, "gemm_nt")):
         r = VGGTTeacherRunner(teacher, dtype=torch.bfloat16, pose_decoder=DL.tiny_pose_decoder, fused_blocks=True, fused_heads=True, fused_tracker=on,
-                              fused_updateformer=uf)
+                              fused_updateformer=uf, tracker_linear=lin)
         toks, ps, _ = r.aggregate(img)
         fm, pitch = r.heads["track_head.feature_extractor"](toks, img, ps, channel_last=True)
         nchw = fm.permute(0, 1, 4, 2, 3)
@@ -583,7 +598,7 @@ def updateformer_section(res, a, dev):
     S, N, D, depth, H = t["S"], t["N"], t["hidden_size"], t["depth"], 8
     with torch.device(dev):
         m = TL.UpdateFormerLayout(depth, depth, 3 * 128 + 4, D, 130, num_heads=H).eval()
-    fused = FusedUpdateFormer(m)
+    fused, fused_tok = FusedUpdateFormer(m), FusedUpdateFormer(m, linear="tokens")
     x = torch.randn(1, N, S, 388, device=dev)
 
     def module_run():
@@ -593,13 +608,16 @@ def updateformer_section(res, a, dev):
     want, got = module_run(), fused(x)[0]
     out["max_abs_diff_vs_module"], out["max_abs_module"] = float((want - got).abs().max()), float(want.abs().max())
     out["launches_per_call"] = fused.launches
-    paths = {"module": module_run, "fused": lambda: fused(x)}
+    out["fused_tokens_max_abs_diff_vs_module"] = float((want - fused_tok(x)[0]).abs().max())
+    out["fused_tokens_launches_per_call"] = fused_tok.launches
+    paths = {"module": module_run, "fused": lambda: fused(x), "fused_tokens": lambda: fused_tok(x)}
     for name, fn in paths.items():
         out[name] = timed(fn, a.warm, a.iters)
     for name, fn in paths.items():
         out[name + "_again"] = timed(fn, 1, a.iters)
     best = lambda k: min(out[k]["median_ms"], out[k + "_again"]["median_ms"])
     out["speedup_fused_vs_module"] = round(best("module") / best("fused"), 3)
+    out["speedup_fused_tokens_vs_module"] = round(best("module") / best("fused_tokens"), 3)
     # the attention kernel alone, on the views the transformer hands it
     n, nv = N + fused.nv, fused.nv
     qkv, q1, kv = torch.randn(n * S, 3 * D, device=dev), torch.randn(n * S, D, device=dev), torch.randn(n * S, 2 * D, device=dev)
@@ -621,23 +639,58 @@ def updateformer_section(res, a, dev):
         out["attention_small"][name] = r
     out["attention_small_us_per_transformer_call"] = round(sum(v["median_ms"] * depth for v in out["attention_small"].values()) * 1e3, 1)
     # the per-kernel split of one fused call: device events around every GEMM (ops.GemmProfiler), LayerNorm and attention by their own timing
-    prof = ops.GemmProfiler()
-    ops.set_gemm_profiler(prof)
-    fused(x)
-    ops.set_gemm_profiler(None)
-    torch.cuda.synchronize()
-    flop, _, launches = prof.totals()
-    by = {}
-    for e0, e1, fl, tag in prof.records:
-        k = f"M={tag[0]} N={tag[1]} K={tag[2]} {tag[4]}"
-        d = by.setdefault(k, {"calls": 0, "ms": 0.0})
-        d["calls"] += 1
-        d["ms"] = round(d["ms"] + e0.elapsed_time(e1), 4)
-    out["fused_gemm"] = {"flop": flop, "launches": launches, "event_ms_total": round(sum(d["ms"] for d in by.values()), 3), "by_shape": by}
+    # (ops.tokens_linear honours the same profiler; its records' epilogue tags start with "t")
+    for key, f in (("fused_gemm", fused), ("fused_tokens_linear", fused_tok)):
+        prof = ops.GemmProfiler()
+        ops.set_gemm_profiler(prof)
+        f(x)
+        ops.set_gemm_profiler(None)
+        torch.cuda.synchronize()
+        flop, _, launches = prof.totals()
+        by = {}
+        for e0, e1, fl, tag in prof.records:
+            k = f"M={tag[0]} N={tag[1]} K={tag[2]} {tag[4]}"
+            d = by.setdefault(k, {"calls": 0, "ms": 0.0})
+            d["calls"] += 1
+            d["ms"] = round(d["ms"] + e0.elapsed_time(e1), 4)
+        out[key] = {"flop": flop, "launches": launches, "event_ms_total": round(sum(d["ms"] for d in by.values()), 3), "by_shape": by}
     xn = torch.randn(n * S, D, device=dev)
     g, b = torch.ones(D, device=dev), torch.zeros(D, device=dev)
     out["layernorm_all_rows"] = timed(lambda: ops.layernorm_fwd(xn, g, b, 1e-5, save_stats=False), a.warm, a.iters, reps=50)
     res["vggt_updateformer"] = out
+
+
+F32_MFMA_TFLOPS = 157.3          # the f32 MFMA peak of one MI355X: 256 CUs x 256 FLOP / clk x 2.4 GHz
+
+
+def tokens_linear_section(res, a, dev):
+    """gd_tokens_linear against gd_gemm_nt, alternating, on the update transformer's products and the tracker's own (each with + bias, + residual)."""
+    from gd_amd.teacher_tracker import FusedTracker
+    trk =FusedTracker(teacher_size_tracker(dev))
+    kpad, hidden = trk.kpad, trk.corr_mlp[0].shape[0]
+    shapes = [(M, K, N, "updateformer") for M in (728, 600, 128) for K, N in ((384, 1152), (384, 768), (384, 384), (384, 1536), (1536, 384), (388, 384), (384, 132))]
+    shapes += [(600, kpad, hidden, "corr_mlp.fc1"), (600, hidden, 128, "corr_mlp.fc2"), (600, 128, 128, "ffeat_updater")]
+    out = {"reps_per_window": 20, "epilogue": "+ bias + residual", "mfma_floor_tflops": F32_MFMA_TFLOPS, "shapes": {}}
+    for M, K, N, what in shapes:
+        x, w, b, r = torch.randn(M, K, device=dev), torch.randn(N, K, device=dev), torch.randn(N, device=dev), torch.randn(M, N, device=dev)
+        y1, y2 = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev)
+        # the new kernel through the C entry point: the Python of ops.tokens_linear (16 us per call) costs more than the kernel; gd_gemm_nt's launches
+        # take longer than its wrapper
+        targs = (_lib.ptr(x), _lib.ptr(w), _lib.ptr(y1), M, N, K, K, K, N, _lib.ptr(b), 0, _lib.ptr(r), N, 0, _lib.stream())
+        fns = {"tokens_linear": lambda: _lib.lib().gd_tokens_linear(*targs), "gemm_nt": lambda: ops.gemm_nt(x, w, y2, bias=b, residual=r)}
+        e = {"what": what, "max_abs_diff": float((ops.tokens_linear(x, w, b, out=y1, residual=r) - fns["gemm_nt"]()).abs().max())}
+        t = {k: [] for k in fns}
+        for _ in range(3):                                                         # alternating: three rounds of each
+            for k, fn in fns.items():
+                t[k].append(timed(fn, a.warm, a.iters, reps=20)["median_ms"])
+        floor_us = 2.0 * M * N * K / (F32_MFMA_TFLOPS * 1e12) * 1e6
+        for k in fns:
+            us = min(t[k]) * 1e3
+            e[k] = {"us": round(us, 2), "tflops": round(2.0 * M * N * K / us / 1e6, 2), "over_mfma_floor": round(us / floor_us, 2)}
+        e["mfma_floor_us"] = round(floor_us, 2)
+        e["speedup_vs_gemm_nt"] = round(e["gemm_nt"]["us"] / e["tokens_linear"]["us"], 2)
+        out["shapes"][f"M={M} K={K} N={N}"] = e
+    res["tokens_linear"] = out
 
 
 MAST3R_HEAD = dict(enc_dim=1024, dec_dim=768, feature_dim=256, last_dim=128, local_feat_dim=24, two_confs=True)
