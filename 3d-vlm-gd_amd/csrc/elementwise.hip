@@ -576,7 +576,10 @@ extern "C" int gd_kp_gather_fwd(const void* const* grids, int ngrid, long bstrid
     GatherParams p = {};
     if (fill_gather(p, grids, ngrid, bstride, grid_dtype, kp, B, Nk, gh, gw, D, sx, sy, img_h, img_w, patch, stride, pitch)) return -1;
     p.out = out;
-    bool vec = (D * gd_dtype_size(grid_dtype)) % 16 == 0 && (bstride * gd_dtype_size(grid_dtype)) % 16 == 0 && ((uintptr_t)out % 16) == 0 && D % 4 == 0;
+    GD_REQUIRE(grid_dtype == GD_F32 || grid_dtype == GD_BF16 || grid_dtype == GD_F16, "gd_kp_gather_fwd: grids are f32, bf16 or f16 (got %d)", grid_dtype);
+    // the 16-byte kernels exist for f32 and bf16 rows; fp16 grids take the scalar kernel, whose ld_rt reads them
+    bool vec = (grid_dtype == GD_F32 || grid_dtype == GD_BF16) && (D * gd_dtype_size(grid_dtype)) % 16 == 0 &&
+               (bstride * gd_dtype_size(grid_dtype)) % 16 == 0 && ((uintptr_t)out % 16) == 0 && D % 4 == 0;
     for (int t = 0; t < ngrid; ++t) vec = vec && ((uintptr_t)grids[t] % 16) == 0;
     if (vec && grid_dtype == GD_BF16) hipLaunchKernelGGL(kp_gather_fwd_vec_kernel<bf16>, dim3(B * Nk), dim3(128), 0, (hipStream_t)stream, p);
     else if (vec) hipLaunchKernelGGL(kp_gather_fwd_vec_kernel<float>, dim3(B * Nk), dim3(128), 0, (hipStream_t)stream, p);
@@ -676,6 +679,7 @@ extern "C" int gd_kp_patch_gather(const void* grid, long bstride, int grid_dtype
     GatherParams p = {};
     const void* one[1] = {grid};
     if (fill_gather(p, one, 1, bstride, grid_dtype, kp, B, Nk, gh, gw, D, sx, sy, img_h, img_w, patch, stride, pitch)) return -1;
+    GD_REQUIRE(grid_dtype == GD_F32 || grid_dtype == GD_BF16, "gd_kp_patch_gather: the grid is f32 or bf16 (got %d)", grid_dtype);
     GD_REQUIRE((D * gd_dtype_size(grid_dtype)) % 16 == 0 && ((uintptr_t)grid % 16) == 0 && ((uintptr_t)out % 16) == 0,
                "gd_kp_patch_gather: token rows must be 16-byte multiples and 16-byte aligned");
     if (grid_dtype == GD_BF16)

@@ -887,6 +887,7 @@ def kp_patch_gather(grid, bstride, kp, B, Nk, gh, gw, D, sx, sy, img_h, img_w, p
         check(lib().gd_kp_patch_gather_h(ptr(grid), bstride, ptr(kp), ptr(out), B, Nk, gh, gw, D, float(sx), float(sy), img_h, img_w, patch,
                                          patch if stride is None else stride, gw if pitch is None else pitch, stream()), "gd_kp_patch_gather_h")
         return out
+    _req(grid.dtype in (torch.float32, torch.bfloat16), "kp_patch_gather: an fp32 or bf16 grid")
     out = torch.empty(B * Nk, 9 * D, dtype=grid.dtype, device=grid.device)
     check(lib().gd_kp_patch_gather(ptr(grid), bstride, dtype_code(grid), ptr(kp), ptr(out), B, Nk, gh, gw, D, float(sx), float(sy),
                                    img_h, img_w, patch, patch if stride is None else stride, gw if pitch is None else pitch,

@@ -242,7 +242,7 @@ int gd_mast3r_head_out(const float* x, const float* w, const float* bias, const 
                        float conf_vmax, int desc_mode, int dconf_mode, float dconf_vmin, float dconf_vmax, void* stream);
 /* interpolate_features (utils/functions.py:55-76) on 1..4 token-major grids, averaged; backward scatters into fp32
  * gradient grids (batch stride bstride elements, pre-zeroed).  pitch = tokens per grid line in memory (gw for a dense grid,
- * gw + 1 for the separator-column layout of gd_stack3_rows' GEMM output). */
+ * gw + 1 for the separator-column layout of gd_stack3_rows' GEMM output).  Grids are f32, bf16 or f16 (f16: the scalar kernel). */
 int gd_kp_gather_fwd(const void* const* grids, int ngrid, long bstride, int grid_dtype, const float* kp, float* out,
                      int B, int Nk, int gh, int gw, int D, float sx, float sy, int img_h, int img_w, int patch,
                      int stride, int pitch, void* stream);
@@ -274,7 +274,7 @@ int gd_kp_gather_bwd_det(void* dgrid, int out_dtype, long bstride, int prefix_ro
 /* get_feature's refine_conv + interpolate_features (src/finetune_timm_vggt.py:319-325) with the two linear maps swapped:
  * out[b*Nk + k][(ky, kx, c)] = bilinear mix (the same four neighbours and weights as gd_kp_gather_fwd) of the 3x3 input patches
  * (zero padding 1) of ONE token grid [gh x pitch, D] -> [B*Nk, 9*D] in the grid's dtype; the conv is then a GEMM over B*Nk rows
- * against the weight packed as [D_out, (ky, kx, c)].  D*elsize must be a multiple of 16 bytes. */
+ * against the weight packed as [D_out, (ky, kx, c)].  The grid is f32 or bf16; D*elsize must be a multiple of 16 bytes. */
 int gd_kp_patch_gather(const void* grid, long bstride, int grid_dtype, const float* kp, void* out, int B, int Nk, int gh,
                        int gw, int D, float sx, float sy, int img_h, int img_w, int patch, int stride, int pitch,
                        void* stream);
