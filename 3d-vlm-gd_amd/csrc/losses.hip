@@ -518,14 +518,17 @@ __global__ __launch_bounds__(256, 2) void pair_rank_tile_kernel(const float* u, 
     const float* ub = u + (long)set * Nmax * 128;
     const int i = i0 + wave * 4 + ps;
     const bool iok = i < n;
+    // a slot past the set still runs the head with its wave (its terms are multiplied by vf = 0 below): it must do so on zeros,
+    // never on the padding row, or 0 * NaN (a padding row that is not finite, or merely huge) reaches du_j, the head gradients and the loss
     float ui[EPL];
 #pragma unroll
     for (int q = 0; q < EPL / 4; ++q) {
         const f32x4 v = *(const f32x4*)(ub + (long)min(i, Nmax - 1) * 128 + k0 + 4 * q);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ui[4 * q + k] = v[k];
+        for (int k = 0; k < 4; ++k) ui[4 * q + k] = iok ? v[k] : 0.f;
     }
-    const float di = depth[(long)set * Nmax + min(i, Nmax - 1)];
+    const float dl = depth[(long)set * Nmax + min(i, Nmax - 1)];
+    const float di = iok ? dl : 0.f;
     float acc[4][EPL], dacc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) { acc[0][e] = acc[1][e] = acc[2][e] = acc[3][e] = 0.f; dacc[e] = 0.f; }

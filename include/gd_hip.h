@@ -328,7 +328,9 @@ int gd_pair_rank(const float* u, const float* depth, const int* counts, const fl
  *                           du_out = 0.5 g_intra[p] du_rank + g_l1[p] du_l1 ([P][2][N][128]; rows written view-major [2][P][N] when view_major), hg_out [516]
  *                           = sum_p 0.5 g_intra[p] (hg_rank[2p] + hg_rank[2p+1]) + g_l1[p] hg_l1[p];
  *   gd_scale_and_transpose: out [B][R][C] = in * g[b] and out_t [B][C][R] = its transpose (smooth-AP backward: dsim g contracted from both sides).
- * gd_pair_rank / gd_depth_l1: gscale may be NULL (= 1 per set). */
+ * gd_pair_rank / gd_depth_l1: gscale may be NULL (= 1 per set).
+ * gd_pair_rank, gd_depth_l1, gd_smooth_ap, gd_smooth_ap_me: rows at or beyond counts[set] (of u, depth, d1, d2, pts3d; rows and columns of sim) never
+ * influence an output, whatever they hold, NaN included.  The corresponding output rows (of du; rows and columns of dsim, rows of row_ws) are written as zeros. */
 int gd_loss_combine_fwd(const float* t0, const float* t1, const float* t2, const float* t3, const float* w4, const int* counts, int P, float* loss,
                         float* terms_out, void* stream);
 int gd_loss_combine_bwd(const float* g, const float* w4, const int* counts, int P, float* grads, void* stream);
