@@ -13,12 +13,16 @@ cross-view distillation target is accumulated by gd_cross_view_attn from the q /
 each selected iteration: no hooks, no [2B, H, n, n] maps, no placeholder.
 
 The modules stay the user's: this class reads their parameters (duck-typed on the attribute names, as teacher_runner.QKCapture does) and
-refuses, with the block's name, anything the kernels do not serve.  Off by default (teacher_runner.VGGTTeacherRunner(fused_blocks=True))."""
+refuses, with the block's name, anything the kernels do not serve.  Off by default (teacher_runner.VGGTTeacherRunner(fused_blocks=True)).
+
+All three stacks are pre-norm ViT blocks: one pack (_ViTBlock, read through teacher_read.Reader) and one body (self_attn, mlp, block) serve
+them; what differs between them is what stands between the QKV GEMM and attention, and the decoder's cross-attention middle."""
 import torch
 
 from . import ops
 from . import teacher_glue as tg
 from ._lib import GdHipError
+from .teacher_read import Reader, f32
 
 
 def fold_layer_scale(linear, ls):
@@ -34,59 +38,118 @@ def fold_layer_scale(linear, ls):
     return g[:, None] * W, (g * b if b is not None else None)
 
 
-class _BlockParams:
-    """One block's tensors in the form the kernels take: matrices in the operand dtype, vectors in fp32."""
+def _attention(r, attn, C, what, rope):
+    """-> (H, RoPE base) of an attention module the kernels serve: head dim 64, scale 64^-0.5, a RoPE module exactly when `rope`."""
+    H = int(r.need(attn, "num_heads", what))
+    if C % H or C // H != 64:
+        r.fail(f"{what}.num_heads", f"head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
+    scale = float(getattr(attn, "scale", 64 ** -0.5))
+    if abs(scale - 64 ** -0.5) > 1e-9:
+        r.fail(f"{what}.scale", f"{scale} is not 64^-0.5")
+    m = getattr(attn, "rope", None)
+    if rope and m is None:            # (named as '<what>.rope is None' after the attention module's path: the wording the GPU tests of CroCo look for)
+        r.fail(what, f"{what}.rope is None: the fused q / k step always rotates")
+    if not rope and m is not None:
+        r.fail(f"{what}.rope", f"{type(m).__name__}: these blocks run without a rotary step")
+    return H, float(getattr(m, "base_frequency", getattr(m, "base", 100.0)))
 
-    def __init__(self, blk, name, dtype, who="FusedAggregatorBlocks", rotary=True):
-        """rotary=False (the DINOv2 embedder's blocks): no q/k norm and no RoPE between the QKV GEMM and attention, so both must be absent."""
-        def need(obj, attr, where):
-            if not hasattr(obj, attr):
-                raise GdHipError(f"{who}: {name}: {where} has no `{attr}`")
-            return getattr(obj, attr)
-        attn, mlp = need(blk, "attn", "the block"), need(blk, "mlp", "the block")
-        H = int(need(attn, "num_heads", "attn"))
-        C = need(attn, "qkv", "attn").weight.shape[1]
-        if C % H or C // H != 64:
-            raise GdHipError(f"{who}: {name}: head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
-        scale = float(getattr(attn, "scale", 64 ** -0.5))
-        if abs(scale - 64 ** -0.5) > 1e-9:
-            raise GdHipError(f"{who}: {name}: attn.scale {scale} is not 64^-0.5")
-        qn, kn = need(attn, "q_norm", "attn"), need(attn, "k_norm", "attn")
-        ln = [isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (64,) for m in (qn, kn)]
-        ident = [isinstance(m, torch.nn.Identity) for m in (qn, kn)]
-        if not rotary and not all(ident):
-            raise GdHipError(f"{who}: {name}: attn.q_norm / attn.k_norm are {type(qn).__name__} / {type(kn).__name__}: served is Identity on both")
-        if not (all(ln) or all(ident)):
-            raise GdHipError(f"{who}: {name}: q_norm / k_norm are {type(qn).__name__} / {type(kn).__name__}: served are "
-                             "LayerNorm(64) with affine on both, or Identity on both")
-        if all(ln) and qn.eps != kn.eps:
-            raise GdHipError(f"{who}: {name}: q_norm and k_norm differ in eps")
-        rope = getattr(attn, "rope", None)
-        if rotary and rope is None:
-            raise GdHipError(f"{who}: {name}: attn.rope is None: the fused q/k step always rotates")
-        if not rotary and rope is not None:
-            raise GdHipError(f"{who}: {name}: attn.rope is {type(rope).__name__}: these blocks run without a rotary step")
-        act = getattr(mlp, "act", None)           # vggt/layers/mlp.py: act_layer(); a layout without the attribute calls F.gelu itself
-        if act is not None and not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
-            raise GdHipError(f"{who}: {name}: mlp.act is {act}: the GEMM epilogue serves exact (erf) GELU")
-        for nm in ("norm1", "norm2"):
-            m = need(blk, nm, "the block")
-            if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (C,)):
-                raise GdHipError(f"{who}: {name}: {nm} is not an affine LayerNorm({C})")
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+
+def _qk_norms(r, attn, qk):
+    """-> ((q gamma, q beta, k gamma, k beta), eps) as gd_qk_norm_rope takes them: four None and 0.0 where q and k are not normed."""
+    plain = (None, None, None, None), 0.0
+    if qk == "rope":
+        return plain
+    qn, kn = r.need(attn, "q_norm", "attn"), r.need(attn, "k_norm", "attn")
+    if all(isinstance(m, torch.nn.Identity) for m in (qn, kn)):
+        return plain
+    are = f"{type(qn).__name__} with k_norm {type(kn).__name__}"
+    if qk is None:
+        r.fail("attn.q_norm", f"{are}: served is Identity on both")
+    if not all(isinstance(m, torch.nn.LayerNorm) for m in (qn, kn)):
+        r.fail("attn.q_norm", f"{are}: served are LayerNorm(64) with affine on both, or Identity on both")
+    (gq, bq, eps), (gk, bk, eps_k) = r.ln(qn, "attn.q_norm", 64), r.ln(kn, "attn.k_norm", 64)
+    if eps != eps_k:
+        r.fail("attn.q_norm", "differs from attn.k_norm in eps")
+    return (gq, bq, gk, bk), eps
+
+
+class _ViTBlock:
+    """One pre-norm ViT block's tensors in the form the kernels take: matrices in the operand dtype, vectors in fp32; LayerScale, where the block
+    has one, folded into proj / fc2.
+    qk: what stands between the QKV GEMM and attention — "norm+rope" (the aggregator: q_norm / k_norm LayerNorm(64) on both or Identity on both,
+    then RoPE), "rope" (CroCo: RoPE alone, no q / k norm in the module) or None (DINOv2: neither; both norms Identity, no rope module).
+    cross: a CroCo decoder block — also `cross_attn` (projq, projk | projv as one [2C, C] matrix, proj), `norm2` in front of it, `norm_y`
+    (LayerNorm, or Identity with norm_mem=False: ny = None), and the MLP's norm is `norm3`."""
+
+    def __init__(self, r, blk, dtype, qk, cross=False):
         op = lambda t: t.detach().to(dtype).contiguous()
-        self.H, self.C = H, C
-        self.base = float(getattr(rope, "base_frequency", getattr(rope, "base", 100.0)))
-        self.n1 = (f32(blk.norm1.weight), f32(blk.norm1.bias), float(blk.norm1.eps))
-        self.n2 = (f32(blk.norm2.weight), f32(blk.norm2.bias), float(blk.norm2.eps))
-        self.wqkv, self.bqkv = op(attn.qkv.weight), f32(attn.qkv.bias)
-        self.qk = (f32(qn.weight), f32(qn.bias), f32(kn.weight), f32(kn.bias)) if all(ln) else (None, None, None, None)
-        self.qk_eps = float(qn.eps) if all(ln) else 0.0
-        wp, bp = fold_layer_scale(need(attn, "proj", "attn"), getattr(blk, "ls1", None))
+        attn, mlp = r.need(blk, "attn"), r.need(blk, "mlp")
+        qkv = r.need(attn, "qkv", "attn")
+        C = self.C = qkv.weight.shape[1]
+        self.rotary = qk is not None
+        self.H, self.base = _attention(r, attn, C, "attn", self.rotary)
+        self.qk, self.qk_eps = _qk_norms(r, attn, qk)
+        r.exact_gelu(getattr(mlp, "act", None), "mlp.act", allow_none=True)
+        self.n1 = r.ln(r.need(blk, "norm1"), "norm1", C)
+        nmlp = "norm3" if cross else "norm2"
+        self.nmlp = r.ln(r.need(blk, nmlp), nmlp, C)
+        self.wqkv, self.bqkv = op(qkv.weight), f32(qkv.bias)
+        wp, bp = fold_layer_scale(r.need(attn, "proj", "attn"), getattr(blk, "ls1", None))
         self.wproj, self.bproj = op(wp), f32(bp)
-        self.w1, self.b1 = op(need(mlp, "fc1", "mlp").weight), f32(mlp.fc1.bias)
-        w2, b2 = fold_layer_scale(need(mlp, "fc2", "mlp"), getattr(blk, "ls2", None))
+        fc1 = r.need(mlp, "fc1", "mlp")
+        self.w1, self.b1 = op(fc1.weight), f32(fc1.bias)
+        w2, b2 = fold_layer_scale(r.need(mlp, "fc2", "mlp"), getattr(blk, "ls2", None))
         self.w2, self.b2 = op(w2), f32(b2)
+        if not cross:
+            return
+        ca = r.need(blk, "cross_attn")
+        pq, pk, pv, po = (r.need(ca, a, "cross_attn") for a in ("projq", "projk", "projv", "proj"))
+        Hc, base_c = _attention(r, ca, C, "cross_attn", True)
+        if (Hc, base_c) != (self.H, self.base):
+            r.fail("cross_attn", f"differs from attn in heads / RoPE base ({Hc}, {base_c:g} against {self.H}, {self.base:g})")
+        if (pk.bias is None) != (pv.bias is None):
+            r.fail("cross_attn.projk", "one of projk and projv has a bias, the other has none")
+        self.n2 = r.ln(r.need(blk, "norm2"), "norm2", C)
+        ny = r.need(blk, "norm_y")
+        self.ny = None if isinstance(ny, torch.nn.Identity) else r.ln(ny, "norm_y", C)
+        self.wq, self.bq = op(pq.weight), f32(pq.bias)
+        # k and v projections of the other view's tokens as ONE GEMM: kv [M, 2C] = [projk | projv], the layout gd_cross_attention_fwd reads
+        self.wkv = op(torch.cat([pk.weight.detach(), pv.weight.detach()], dim=0))
+        self.bkv = None if pk.bias is None else f32(torch.cat([pk.bias.detach(), pv.bias.detach()]))
+        self.wcproj, self.bcproj = op(po.weight), f32(po.bias)
+
+
+def _blocks(who, prefix, blocks, dtype, qk, cross=False):
+    return [_ViTBlock(Reader(who, f"{prefix}[{i}]"), b, dtype, qk, cross) for i, b in enumerate(blocks)]
+
+
+def _operand_dtype(who, dtype):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise GdHipError(f"{who}: dtype must be torch.float32 or torch.bfloat16")
+    return dtype
+
+
+def self_attn(p, x, pos, B, N, dtype, want_qk=False):
+    """x [B*N, C] fp32 residual stream -> (x + proj(attention(norm1(x))) fp32, the (q, k) qk_norm_rope hands out with want_qk, else None)."""
+    y, _, _ = ops.layernorm_fwd(x, *p.n1, save_stats=False, out_dtype=dtype)
+    qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
+    # in place on qkv; null gamma / beta (CroCo, an Identity-normed aggregator block): plain RoPE of q and k.  Without a rotary step
+    # attention_fwd reads the packed qkv as the GEMM wrote it.
+    qk = ops.qk_norm_rope(qkv, B, N, p.H, pos, *p.qk, p.qk_eps, p.base, want_qk=want_qk) if p.rotary else None
+    o, _ = ops.attention_fwd(qkv, B, N, p.H)
+    return ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x), qk
+
+
+def mlp(p, x, dtype):
+    y, _, _ = ops.layernorm_fwd(x, *p.nmlp, save_stats=False, out_dtype=dtype)
+    h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
+    return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x)
+
+
+def block(p, x, pos, B, N, dtype, want_qk=False):
+    """x [B*N, C] fp32 residual stream -> (x after the block, (q, k) or None)."""
+    x, qk = self_attn(p, x, pos, B, N, dtype, want_qk)
+    return mlp(p, x, dtype), qk
 
 
 class FusedAggregatorBlocks:
@@ -97,37 +160,26 @@ class FusedAggregatorBlocks:
     residual and write fp32.  torch.float32: everything exact fp32, the parity mode."""
 
     def __init__(self, aggregator, dtype=torch.bfloat16):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise GdHipError("FusedAggregatorBlocks: dtype must be torch.float32 or torch.bfloat16")
-        for a in ("frame_blocks", "global_blocks", "patch_start_idx"):
-            if not hasattr(aggregator, a):
-                raise GdHipError(f"FusedAggregatorBlocks: the aggregator has no `{a}`")
+        who, r = "FusedAggregatorBlocks", Reader("FusedAggregatorBlocks", "aggregator")
+        self.dtype = _operand_dtype(who, dtype)
+        frame, glob = r.need(aggregator, "frame_blocks"), r.need(aggregator, "global_blocks")
         order = list(getattr(aggregator, "aa_order", ["frame", "global"]))
         if order != ["frame", "global"]:
-            raise GdHipError(f"FusedAggregatorBlocks: aa_order {order}: served is ['frame', 'global']")
-        self.dtype = dtype
+            r.fail("aa_order", f"{order}: served is ['frame', 'global']")
         self.per = int(getattr(aggregator, "aa_block_size", 1))
-        depth = len(aggregator.frame_blocks)
-        if len(aggregator.global_blocks) != depth or depth % self.per:
-            raise GdHipError(f"FusedAggregatorBlocks: {depth} frame / {len(aggregator.global_blocks)} global blocks do not pair up in groups of {self.per}")
+        depth = len(frame)
+        if len(glob) != depth or depth % self.per:
+            r.fail("frame_blocks", f"{depth} frame / {len(glob)} global blocks do not pair up in groups of {self.per}")
         # aggregator.py:255-260 keeps the map of iteration i `if i in self.attn_indices`: an index past the last iteration never matches
         self.attn_indices = sorted({int(i) for i in (getattr(aggregator, "attn_indices", None) or []) if 0 <= int(i) < depth // self.per})
         self.temperature = float(getattr(aggregator, "temperature", 1.0))
-        self.prefix = int(aggregator.patch_start_idx)
-        self.frame = [_BlockParams(b, f"frame_blocks[{i}]", dtype) for i, b in enumerate(aggregator.frame_blocks)]
-        self.glob = [_BlockParams(b, f"global_blocks[{i}]", dtype) for i, b in enumerate(aggregator.global_blocks)]
+        self.prefix = int(r.need(aggregator, "patch_start_idx"))
+        self.frame = _blocks(who, "frame_blocks", frame, dtype, "norm+rope")
+        self.glob = _blocks(who, "global_blocks", glob, dtype, "norm+rope")
 
     def _block(self, p, x, pos, B, N, want_qk=False):
-        """x [B*N, C] fp32 residual stream -> (x after the block, (q, k) or None)."""
-        dt = self.dtype
-        y, _, _ = ops.layernorm_fwd(x, p.n1[0], p.n1[1], p.n1[2], save_stats=False, out_dtype=dt)
-        qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
-        qk = ops.qk_norm_rope(qkv, B, N, p.H, pos, *p.qk, p.qk_eps, p.base, want_qk=want_qk)
-        o, _ = ops.attention_fwd(qkv, B, N, p.H)
-        x = ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x)
-        y, _, _ = ops.layernorm_fwd(x, p.n2[0], p.n2[1], p.n2[2], save_stats=False, out_dtype=dt)
-        h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
-        return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x), qk
+        """One block alone (what the per-block tests call; `forward` calls `block` itself)."""
+        return block(p, x, pos, B, N, self.dtype, want_qk)
 
     @torch.no_grad()
     def forward(self, tokens, pos, B, S):
@@ -146,10 +198,10 @@ class FusedAggregatorBlocks:
         for it in range(len(self.frame) // self.per):
             inter = []
             for j in range(it * self.per, (it + 1) * self.per):
-                x, _ = self._block(self.frame[j], x, pos, BS, P)
+                x, _ = block(self.frame[j], x, pos, BS, P, self.dtype)
                 inter.append(x)
             for k, j in enumerate(range(it * self.per, (it + 1) * self.per)):
-                x, qk = self._block(self.glob[j], x, pos, B, S * P, want_qk=j in sel)
+                x, qk = block(self.glob[j], x, pos, B, S * P, self.dtype, j in sel)
                 if qk is not None:
                     maps = tg.cross_view_attention_maps(qk[0], qk[1], 64 ** -0.5, self.temperature, self.prefix, out=maps,
                                                         weight=1.0 / (self.glob[j].H * len(sel)), accumulate=nsel > 0)
@@ -181,58 +233,49 @@ class FusedDinoEmbed:
     WHO = "FusedDinoEmbed"
 
     def __init__(self, embedder, dtype=torch.bfloat16, name="aggregator.patch_embed"):
-        who = self.WHO
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise GdHipError(f"{who}: dtype must be torch.float32 or torch.bfloat16")
-
-        def need(obj, attr, where):
-            if not hasattr(obj, attr):
-                raise GdHipError(f"{who}: {where} has no `{attr}`")
-            return getattr(obj, attr)
+        who, r = self.WHO, Reader(self.WHO, name)
+        fail, need = r.fail, r.need
+        _operand_dtype(who, dtype)
         blocks = getattr(embedder, "blocks", None)
         if blocks is None:
-            raise GdHipError(f"{who}: {name} has no `blocks` (the 'conv' patch embedder is one convolution: leave fused_patch_embed off)")
+            fail("blocks", "missing (the 'conv' patch embedder is one convolution: leave fused_patch_embed off)")
         if getattr(embedder, "chunked_blocks", False):
-            raise GdHipError(f"{who}: {name}.chunked_blocks is true: served is a flat block list (block_chunks=0)")
-        pos_embed = need(embedder, "pos_embed", name)
-        D = int(pos_embed.shape[-1])
+            fail("chunked_blocks", "true: served is a flat block list (block_chunks=0)")
+        D = int(need(embedder, "pos_embed").shape[-1])
         if D % 8 or D > 2048:
-            raise GdHipError(f"{who}: {name}.pos_embed has width {D}: served is a multiple of 8 up to 2048")
-        P = need(embedder, "patch_size", name)
+            fail("pos_embed", f"width {D}: served is a multiple of 8 up to 2048")
+        P = need(embedder, "patch_size")
         P = int(P[0] if isinstance(P, (tuple, list)) else P)
-        proj = need(need(embedder, "patch_embed", name), "proj", f"{name}.patch_embed")
+        pe = need(embedder, "patch_embed")
+        proj = need(pe, "proj", "patch_embed")
         if not (isinstance(proj, torch.nn.Conv2d) and tuple(proj.kernel_size) == (P, P) and tuple(proj.stride) == (P, P) and
                 tuple(proj.padding) == (0, 0) and tuple(proj.dilation) == (1, 1) and proj.groups == 1 and proj.in_channels == 3 and
                 proj.out_channels == D):
-            raise GdHipError(f"{who}: {name}.patch_embed.proj is {proj}: served is Conv2d(3, {D}, kernel_size={P}, stride={P})")
-        if not isinstance(getattr(embedder.patch_embed, "norm", None), (torch.nn.Identity, type(None))):
-            raise GdHipError(f"{who}: {name}.patch_embed.norm is {type(embedder.patch_embed.norm).__name__}: served is Identity")
-        R = int(need(embedder, "num_register_tokens", name))
+            fail("patch_embed.proj", f"{proj}: served is Conv2d(3, {D}, kernel_size={P}, stride={P})")
+        if not isinstance(getattr(pe, "norm", None), (torch.nn.Identity, type(None))):
+            fail("patch_embed.norm", f"{type(pe.norm).__name__}: served is Identity")
+        R = int(need(embedder, "num_register_tokens"))
         reg = getattr(embedder, "register_tokens", None)
         if (0 if reg is None else int(reg.shape[-2])) != R or (reg is not None and int(reg.shape[-1]) != D):
-            raise GdHipError(f"{who}: {name}.register_tokens {None if reg is None else tuple(reg.shape)} disagrees with num_register_tokens = {R} at width {D}")
-        cls = need(embedder, "cls_token", name)
+            fail("register_tokens", f"{None if reg is None else tuple(reg.shape)} disagrees with num_register_tokens = {R} at width {D}")
+        cls = need(embedder, "cls_token")
         if cls.numel() != D:
-            raise GdHipError(f"{who}: {name}.cls_token {tuple(cls.shape)} is not one token of width {D}")
+            fail("cls_token", f"{tuple(cls.shape)} is not one token of width {D}")
         if not callable(getattr(embedder, "interpolate_pos_encoding", None)):
-            raise GdHipError(f"{who}: {name} has no `interpolate_pos_encoding`")
-        norm = need(embedder, "norm", name)
-        if not (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and tuple(norm.normalized_shape) == (D,)):
-            raise GdHipError(f"{who}: {name}.norm is not an affine LayerNorm({D})")
-        self.blocks = [_BlockParams(b, f"{name}.blocks[{i}]", dtype, who=who, rotary=False) for i, b in enumerate(blocks)]
+            fail("interpolate_pos_encoding", "missing")
+        self.norm = r.ln(need(embedder, "norm"), "norm", D)
+        self.blocks = _blocks(who, f"{name}.blocks", blocks, dtype, None)
         for i, p in enumerate(self.blocks):
             if p.C != D:
-                raise GdHipError(f"{who}: {name}.blocks[{i}]: width {p.C} is not the embedder's {D}")
-        f32 = lambda t: t.detach().float().contiguous()
+                fail(f"blocks[{i}].attn.qkv", f"width {p.C} is not the embedder's {D}")
         self.embedder, self.name, self.dtype, self.D, self.P, self.R = embedder, name, dtype, D, P, R
         K = 3 * P * P
         self.Kp = (K + 63) // 64 * 64                                 # the patch convolution as a [D, Kp] matrix (vit.GDViT._patch_plan)
         wp = torch.zeros(D, self.Kp, dtype=torch.float32, device=proj.weight.device)
         wp[:, :K] = proj.weight.detach().float().reshape(D, K)
-        self.wpe, self.bpe = wp.to(dtype).contiguous(), None if proj.bias is None else f32(proj.bias)
+        self.wpe, self.bpe = wp.to(dtype).contiguous(), f32(proj.bias)
         self.cls = f32(cls).reshape(D)
         self.reg = None if reg is None else f32(reg).reshape(R, D)
-        self.norm = (f32(norm.weight), f32(norm.bias), float(norm.eps))
         self._pos_cache, self._agg_norm = {}, None
 
     # -- pieces ---------------------------------------------------------------------------------------------------------------------
@@ -249,17 +292,6 @@ class FusedDinoEmbed:
                 raise GdHipError(f"{self.WHO}: {self.name}.interpolate_pos_encoding returned {tuple(pe.shape)}, expected {(1, 1 + gh * gw, self.D)}")
             self._pos_cache[key] = pe.detach().float()[0].contiguous()
         return self._pos_cache[key]
-
-    def _block(self, p, x, B, N):
-        """x [B*N, D] fp32 residual stream -> the same after one block (attention_fwd reads the packed qkv as the GEMM wrote it)."""
-        dt = self.dtype
-        y, _, _ = ops.layernorm_fwd(x, p.n1[0], p.n1[1], p.n1[2], save_stats=False, out_dtype=dt)
-        qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
-        o, _ = ops.attention_fwd(qkv, B, N, p.H)
-        x = ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x)
-        y, _, _ = ops.layernorm_fwd(x, p.n2[0], p.n2[1], p.n2[2], save_stats=False, out_dtype=dt)
-        h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
-        return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x)
 
     def _grid(self, H, W):
         if H % self.P or W % self.P or H < self.P or W < self.P:
@@ -282,7 +314,7 @@ class FusedDinoEmbed:
         tok = ops.gemm_nt(col, self.wpe, bias=self.bpe)
         x = ops.dino_assemble_tokens(tok, self.cls, self.reg, self._pos(H, W, gh, gw), BS, Np).view(BS * Nt, self.D)
         for p in self.blocks:
-            x = self._block(p, x, BS, Nt)
+            x, _ = block(p, x, None, BS, Nt, self.dtype)
         return x.view(BS, Nt, self.D)
 
     @torch.no_grad()
@@ -298,19 +330,15 @@ class FusedDinoEmbed:
 
     def check_aggregator(self, aggregator):
         """-> (camera [2, D], regs [2, Rg, D] or None, prefix) of an aggregator this embedder can feed; refuses, naming the attribute, otherwise."""
-        who = self.WHO
-        for a in ("camera_token", "register_token", "patch_start_idx", "_resnet_mean", "_resnet_std"):
-            if not hasattr(aggregator, a):
-                raise GdHipError(f"{who}: the aggregator has no `{a}`")
-        prefix = int(aggregator.patch_start_idx)
+        r = Reader(self.WHO, "aggregator")
+        cam, reg, prefix, _, _ = (r.need(aggregator, a) for a in ("camera_token", "register_token", "patch_start_idx", "_resnet_mean", "_resnet_std"))
+        prefix = int(prefix)
         if prefix < 1:
-            raise GdHipError(f"{who}: aggregator.patch_start_idx = {prefix}: served is a camera token (and registers) in front of the patches")
-        cam, reg = aggregator.camera_token, aggregator.register_token
+            r.fail("patch_start_idx", f"{prefix}: served is a camera token (and registers) in front of the patches")
         if cam.shape[-1] != self.D or tuple(cam.shape[:3]) != (1, 2, 1):
-            raise GdHipError(f"{who}: aggregator.camera_token {tuple(cam.shape)}: the embedder's width is {self.D} (expected [1, 2, 1, {self.D}])")
+            r.fail("camera_token", f"{tuple(cam.shape)}: the embedder's width is {self.D} (expected [1, 2, 1, {self.D}])")
         if tuple(reg.shape) != (1, 2, prefix - 1, self.D):
-            raise GdHipError(f"{who}: aggregator.register_token {tuple(reg.shape)} does not fit patch_start_idx = {prefix} at width {self.D}")
-        f32 = lambda t: t.detach().float().contiguous()
+            r.fail("register_token", f"{tuple(reg.shape)} does not fit patch_start_idx = {prefix} at width {self.D}")
         return f32(cam).reshape(2, self.D), (f32(reg).reshape(2, prefix - 1, self.D) if prefix > 1 else None), prefix
 
     @torch.no_grad()
@@ -336,72 +364,6 @@ class FusedDinoEmbed:
 _WHO = "FusedCroCoBlocks"
 
 
-def _need(obj, attr, name, where):
-    if not hasattr(obj, attr):
-        raise GdHipError(f"{_WHO}: {name}: {where} has no `{attr}`")
-    return getattr(obj, attr)
-
-
-def _affine_ln(m, C, name, nm):
-    if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and tuple(m.normalized_shape) == (C,)):
-        raise GdHipError(f"{_WHO}: {name}: {nm} is not an affine LayerNorm({C})")
-    return m.weight.detach().float().contiguous(), m.bias.detach().float().contiguous(), float(m.eps)
-
-
-def _heads_scale_rope(attn, C, name, what):
-    """-> (H, rope base) of an attention module the kernels serve: head dim 64, scale 64^-0.5, a RoPE module."""
-    H = int(_need(attn, "num_heads", name, what))
-    if C % H or C // H != 64:
-        raise GdHipError(f"{_WHO}: {name}: {what}: head dim {C / H:g} (width {C}, {H} heads): the attention kernels serve head dim 64")
-    scale = float(getattr(attn, "scale", 64 ** -0.5))
-    if abs(scale - 64 ** -0.5) > 1e-9:
-        raise GdHipError(f"{_WHO}: {name}: {what}.scale {scale} is not 64^-0.5")
-    rope = getattr(attn, "rope", None)
-    if rope is None:
-        raise GdHipError(f"{_WHO}: {name}: {what}.rope is None: the fused q / k step always rotates")
-    return H, float(getattr(rope, "base_frequency", getattr(rope, "base", 100.0)))
-
-
-class _CroCoBlockParams:
-    """One CroCo block's tensors in the form the kernels take (matrices in the operand dtype, vectors in fp32).  `decoder`: the block also
-    has `cross_attn` (projq / projk / projv / proj), `norm_y` (LayerNorm, or Identity with norm_mem=False) and `norm3`."""
-
-    def __init__(self, blk, name, dtype, decoder):
-        attn, mlp = _need(blk, "attn", name, "the block"), _need(blk, "mlp", name, "the block")
-        C = _need(attn, "qkv", name, "attn").weight.shape[1]
-        self.C = C
-        self.H, self.base = _heads_scale_rope(attn, C, name, "attn")
-        act = getattr(mlp, "act", None)
-        if act is not None and not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
-            raise GdHipError(f"{_WHO}: {name}: mlp.act is {act}: the GEMM epilogue serves exact (erf) GELU")
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        op = lambda t: t.detach().to(dtype).contiguous()
-        self.n1 = _affine_ln(_need(blk, "norm1", name, "the block"), C, name, "norm1")
-        self.nmlp = _affine_ln(_need(blk, "norm3" if decoder else "norm2", name, "the block"), C, name, "norm3" if decoder else "norm2")
-        self.wqkv, self.bqkv = op(attn.qkv.weight), f32(attn.qkv.bias)
-        proj = _need(attn, "proj", name, "attn")
-        self.wproj, self.bproj = op(proj.weight), f32(proj.bias)
-        self.w1, self.b1 = op(_need(mlp, "fc1", name, "mlp").weight), f32(mlp.fc1.bias)
-        self.w2, self.b2 = op(_need(mlp, "fc2", name, "mlp").weight), f32(mlp.fc2.bias)
-        if not decoder:
-            return
-        ca = _need(blk, "cross_attn", name, "the block")
-        pq, pk, pv, po = (_need(ca, a, name, "cross_attn") for a in ("projq", "projk", "projv", "proj"))
-        Hc, base_c = _heads_scale_rope(ca, C, name, "cross_attn")
-        if (Hc, base_c) != (self.H, self.base):
-            raise GdHipError(f"{_WHO}: {name}: attn and cross_attn differ in heads / RoPE base ({self.H}, {self.base:g} against {Hc}, {base_c:g})")
-        if (pk.bias is None) != (pv.bias is None):
-            raise GdHipError(f"{_WHO}: {name}: cross_attn.projk and projv differ in having a bias")
-        self.n2 = _affine_ln(_need(blk, "norm2", name, "the block"), C, name, "norm2")
-        ny = _need(blk, "norm_y", name, "the block")
-        self.ny = None if isinstance(ny, torch.nn.Identity) else _affine_ln(ny, C, name, "norm_y")
-        self.wq, self.bq = op(pq.weight), f32(pq.bias)
-        # k and v projections of the other view's tokens as ONE GEMM: kv [M, 2C] = [projk | projv], the layout gd_cross_attention_fwd reads
-        self.wkv = op(torch.cat([pk.weight.detach(), pv.weight.detach()], dim=0))
-        self.bkv = None if pk.bias is None else f32(torch.cat([pk.bias.detach(), pv.bias.detach()]))
-        self.wcproj, self.bcproj = op(po.weight), f32(po.bias)
-
-
 class FusedCroCoBlocks:
     """FusedCroCoBlocks(matcher, dtype=torch.float32): the MASt3R teacher's 24 encoder blocks and 12 + 12 decoder blocks (AsymmetricCroCo3DStereo:
     `enc_blocks`, `decoder_embed`, `dec_blocks`, `dec_blocks2`, `dec_norm`) on the HIP kernels.  The modules stay the user's: their parameters
@@ -418,53 +380,35 @@ class FusedCroCoBlocks:
     keep_logits path work on them as they are."""
 
     def __init__(self, matcher, dtype=torch.float32):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise GdHipError(f"{_WHO}: dtype must be torch.float32 or torch.bfloat16")
-        for a in ("enc_blocks", "decoder_embed", "dec_blocks", "dec_blocks2", "dec_norm"):
-            if not hasattr(matcher, a):
-                raise GdHipError(f"{_WHO}: the matcher has no `{a}`")
-        if len(matcher.dec_blocks) != len(matcher.dec_blocks2):
-            raise GdHipError(f"{_WHO}: dec_blocks ({len(matcher.dec_blocks)}) and dec_blocks2 ({len(matcher.dec_blocks2)}) differ in length")
-        if len(matcher.dec_blocks) == 0:
-            raise GdHipError(f"{_WHO}: dec_blocks is empty")
-        self.dtype = dtype
-        self.enc = [_CroCoBlockParams(b, f"enc_blocks[{i}]", dtype, False) for i, b in enumerate(matcher.enc_blocks)]
-        self.dec1 = [_CroCoBlockParams(b, f"dec_blocks[{i}]", dtype, True) for i, b in enumerate(matcher.dec_blocks)]
-        self.dec2 = [_CroCoBlockParams(b, f"dec_blocks2[{i}]", dtype, True) for i, b in enumerate(matcher.dec_blocks2)]
-        de = matcher.decoder_embed
-        if not isinstance(de, torch.nn.Linear):
-            raise GdHipError(f"{_WHO}: decoder_embed is {type(de).__name__}, not a Linear")
-        self.wde = de.weight.detach().to(dtype).contiguous()
-        self.bde = None if de.bias is None else de.bias.detach().float().contiguous()
-        Cd = de.weight.shape[0]
-        for p, nm in [(p, f"dec_blocks[{i}]") for i, p in enumerate(self.dec1)] + [(p, f"dec_blocks2[{i}]") for i, p in enumerate(self.dec2)]:
-            if p.C != Cd:
-                raise GdHipError(f"{_WHO}: {nm}: width {p.C} is not decoder_embed's {Cd}")
-        self.dnorm = _affine_ln(matcher.dec_norm, Cd, "dec_norm", "dec_norm")
+        r = Reader(_WHO, "matcher")
+        self.dtype = _operand_dtype(_WHO, dtype)
+        enc, de, dec1, dec2, dnorm = (r.need(matcher, a) for a in ("enc_blocks", "decoder_embed", "dec_blocks", "dec_blocks2", "dec_norm"))
+        if len(dec1) != len(dec2):
+            r.fail("dec_blocks", f"{len(dec1)} blocks and the {len(dec2)} of dec_blocks2 differ in length")
+        if len(dec1) == 0:
+            r.fail("dec_blocks", "empty")
+        self.enc = _blocks(_WHO, "enc_blocks", enc, dtype, "rope")
+        self.dec1 = _blocks(_WHO, "dec_blocks", dec1, dtype, "rope", cross=True)
+        self.dec2 = _blocks(_WHO, "dec_blocks2", dec2, dtype, "rope", cross=True)
+        self.wde, self.bde = r.linear(de, "decoder_embed", cast=lambda t: t.detach().to(dtype).contiguous())
+        Cd = self.wde.shape[0]
+        for nm, stack in (("dec_blocks", self.dec1), ("dec_blocks2", self.dec2)):
+            for i, p in enumerate(stack):
+                if p.C != Cd:
+                    Reader(_WHO, f"{nm}[{i}]").fail("attn.qkv", f"width {p.C} is not decoder_embed's {Cd}")
+        self.dnorm = r.ln(dnorm, "dec_norm", Cd)
 
     # -- pieces ---------------------------------------------------------------------------------------------------------------------
-    def _self_attn(self, p, x, pos, B, N):
-        y, _, _ = ops.layernorm_fwd(x, *p.n1, save_stats=False, out_dtype=self.dtype)
-        qkv = ops.gemm_nt(y, p.wqkv, bias=p.bqkv)
-        ops.qk_norm_rope(qkv, B, N, p.H, pos, None, None, None, None, 0.0, p.base)      # null gamma / beta: plain RoPE of q and k
-        o, _ = ops.attention_fwd(qkv, B, N, p.H)
-        return ops.gemm_nt(o, p.wproj, out_dtype=torch.float32, bias=p.bproj, residual=x)
-
-    def _mlp(self, p, x):
-        y, _, _ = ops.layernorm_fwd(x, *p.nmlp, save_stats=False, out_dtype=self.dtype)
-        h = ops.gemm_nt(y, p.w1, bias=p.b1, act=1)
-        return ops.gemm_nt(h, p.w2, out_dtype=torch.float32, bias=p.b2, residual=x)
-
     def _enc_block(self, p, x, pos, B, N):
-        """x [B*N, C] fp32 residual stream -> the same after one encoder block."""
-        return self._mlp(p, self._self_attn(p, x, pos, B, N))
+        """x [B*N, C] fp32 residual stream -> the same after one encoder block (what the per-block tests call; `encode` calls `block` itself)."""
+        return block(p, x, pos, B, N, self.dtype)[0]
 
     def _dec_block(self, p, x, y, xpos, ypos, B, Nx, Ny):
         """x [B*Nx, C], y [B*Ny, C] fp32 (this view's tokens, the other view's: read only) -> (x after the block, camap [B, 1, Nx, Ny] fp32:
         the head mean of the raw scaled scores)."""
         from .rope import rope_2d
         dt, C, H = self.dtype, p.C, p.H
-        x = self._self_attn(p, x, xpos, B, Nx)
+        x, _ = self_attn(p, x, xpos, B, Nx, dt)
         xn, _, _ = ops.layernorm_fwd(x, *p.n2, save_stats=False, out_dtype=dt)
         q = ops.gemm_nt(xn, p.wq, bias=p.bq)
         if p.ny is not None:
@@ -477,7 +421,7 @@ class FusedCroCoBlocks:
         camap = ops.gemm_nt(q.view(B, Nx, C), kv.view(B, Ny, 2 * C)[:, :, :C], out_dtype=torch.float32, alpha=64 ** -0.5 / H)
         o, _ = ops.cross_attention_fwd(q, kv, B, Nx, Ny, H)
         x = ops.gemm_nt(o, p.wcproj, out_dtype=torch.float32, bias=p.bcproj, residual=x)
-        return self._mlp(p, x), camap.unsqueeze(1)
+        return mlp(p, x, dt), camap.unsqueeze(1)
 
     @staticmethod
     def _flat(x, pos, C, what):
@@ -492,7 +436,7 @@ class FusedCroCoBlocks:
         """x [B, N, C] (after the patch embedding), pos [B, N, 2] (y, x) -> [B, N, C] fp32 after all `enc_blocks` (`enc_norm` stays the user's)."""
         t, p2, B, N = self._flat(x, pos, self.enc[0].C if self.enc else x.shape[-1], "encode")
         for p in self.enc:
-            t = self._enc_block(p, t, p2, B, N)
+            t, _ = block(p, t, p2, B, N, self.dtype)
         return t.view(B, N, -1)
 
     @torch.no_grad()

@@ -18,7 +18,7 @@ A residual unit whose activation is ReLU(inplace=True) â€” the VGGT teacher's â€
 `activation.inplace` flag is honoured: in place, the producer of x rectifies (GEMM epilogue / resample flag); out of place â€” the MASt3R teacher's â€”
 the operand producer does (gd_grid_resample at identity size with the ReLU flag) and the skip stays x.
 
-The modules stay the user's: these classes read their parameters (duck-typed on the attribute names, as teacher_blocks._BlockParams does), pack them
+The modules stay the user's: these classes read their parameters (duck-typed on the attribute names, through teacher_read.Reader as teacher_blocks._ViTBlock does), pack them
 once into the operand layout, and refuse, naming the attribute, anything the kernels do not serve.  Off by default
 (teacher_runner.VGGTTeacherRunner(fused_heads=True), teacher_runner.MASt3RTeacherRunner(fused_heads=True)).
 
@@ -32,6 +32,7 @@ import torch
 
 from . import ops
 from ._lib import GdHipError
+from .teacher_read import Reader, f32, to_device
 
 
 def _sincos(coords, channels):
@@ -62,7 +63,6 @@ def pack_pixel_shuffle(t, patch):
 
 
 _pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-_f32 = lambda t: None if t is None else t.detach().float().contiguous()
 
 
 class _Unit:
@@ -70,7 +70,7 @@ class _Unit:
 
 
 class _FusedHead:
-    """What FusedDPTHead and FusedMASt3RHead share.  Reading: `_fail` / `_need` / `_chan` and the packers `_pack_conv`, `_pack_resize`,
+    """What FusedDPTHead and FusedMASt3RHead share.  Reading: `_fail` / `_need` (the teacher_read.Reader's), `_chan` and the packers `_pack_conv`, `_pack_resize`,
     `_pack_unit`, `_pack_fusion` (a refusal reads '<class>: <name>.<attribute>: <why>').  Running: `_op`, `_stack`, `_conv3`, `_unit`, `_level`, `_fuse`
     on `frames` pitched grids at once.  A subclass fills self.resize, self.rn, self.fusion (four entries each) and self.features."""
 
@@ -78,16 +78,11 @@ class _FusedHead:
         if dtype not in (torch.float32, torch.bfloat16):
             raise GdHipError(f"{type(self).__name__}: dtype must be torch.float32 or torch.bfloat16")
         self.dtype, self.name = dtype, name
+        r = self._r = Reader(type(self).__name__, name)
+        # a head's attribute that is present and None is the module's own value (pos_embed, feature_only, conf_mode, ...): only an absent one is missing
+        self._fail, self._need = r.fail, functools.partial(r.need, none_ok=True)
 
     # ---- reading the module -------------------------------------------------------------------------------------------------------
-    def _fail(self, attr, why):
-        raise GdHipError(f"{type(self).__name__}: {self.name}.{attr}: {why}")
-
-    def _need(self, obj, attr, where):
-        if not hasattr(obj, attr):
-            self._fail(f"{where}.{attr}" if where else attr, "missing")
-        return getattr(obj, attr)
-
     def _to_op(self, t):
         return t.detach().to(self.dtype).contiguous()
 
@@ -107,7 +102,7 @@ class _FusedHead:
         self._chan(m.in_channels, attr)
         if not any_out:
             self._chan(m.out_channels, attr)
-        return self._to_op(m.weight.permute(0, 3, 2, 1).reshape(m.out_channels, k * k * m.in_channels)), _f32(m.bias)
+        return self._to_op(m.weight.permute(0, 3, 2, 1).reshape(m.out_channels, k * k * m.in_channels)), f32(m.bias)
 
     def _pack_resize(self, m, attr, c, src):
         """A level's resize module after its 1x1 projection of c channels (`src` names the projection in a refusal) -> the self.resize entry."""
@@ -119,7 +114,7 @@ class _FusedHead:
                     or _pair(m.dilation) != (1, 1) or k > 8 or m.in_channels != c):
                 self._fail(attr, "served is a ConvTranspose2d with kernel = stride <= 8, no padding, groups = 1")
             self._chan(m.out_channels, attr)
-            bias = _f32(m.bias) if m.bias is not None else torch.zeros(m.out_channels, dtype=torch.float32, device=m.weight.device)
+            bias = f32(m.bias) if m.bias is not None else torch.zeros(m.out_channels, dtype=torch.float32, device=m.weight.device)
             # weight [c, n, ky, kx] -> [(ky, kx, n), c]: the GEMM's columns in the order gd_deconv_scatter reads them
             return ("deconv", m.out_channels, k, self._to_op(m.weight.permute(2, 3, 1, 0).reshape(k * k * m.out_channels, c)), bias)
         if isinstance(m, torch.nn.Conv2d):
@@ -243,25 +238,22 @@ class FusedDPTHead(_FusedHead):
     def __init__(self, head, dtype=torch.float32, name="head"):
         super().__init__(dtype, name)
         fail, need, conv = self._fail, self._need, self._pack_conv
-        self.patch = int(need(head, "patch_size", ""))
-        self.layer_idx = [int(i) for i in need(head, "intermediate_layer_idx", "")]
-        self.pos_embed, self.feature_only = bool(need(head, "pos_embed", "")), bool(need(head, "feature_only", ""))
-        self.down_ratio = need(head, "down_ratio", "")
+        self.patch = int(need(head, "patch_size"))
+        self.layer_idx = [int(i) for i in need(head, "intermediate_layer_idx")]
+        self.pos_embed, self.feature_only = bool(need(head, "pos_embed")), bool(need(head, "feature_only"))
+        self.down_ratio = need(head, "down_ratio")
         if len(self.layer_idx) != 4:
             fail("intermediate_layer_idx", f"{len(self.layer_idx)} entries: the head fuses four levels")
         if not self.feature_only:
-            self.activation, self.conf_activation = need(head, "activation", ""), need(head, "conf_activation", "")
+            self.activation, self.conf_activation = need(head, "activation"), need(head, "conf_activation")
             if self.activation not in ops.DPT_ACT:
                 fail("activation", f"{self.activation!r}: gd_dpt_head_out serves {sorted(ops.DPT_ACT)}")
             if self.conf_activation not in ops.DPT_CONF_ACT or self.conf_activation == "linear":
                 fail("conf_activation", f"{self.conf_activation!r}: gd_dpt_head_out serves ['expp0', 'expp1', 'sigmoid']")
-        norm = need(head, "norm", "")
-        if not (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and len(norm.normalized_shape) == 1):
-            fail("norm", "is not an affine LayerNorm over the token width")
-        self.norm = (_f32(norm.weight), _f32(norm.bias), float(norm.eps))
-        dim_in = norm.normalized_shape[0]
+        self.norm = self._r.ln(need(head, "norm"), "norm")
+        dim_in = head.norm.normalized_shape[0]
         self._chan(dim_in, "norm")
-        projects, resize, scratch = need(head, "projects", ""), need(head, "resize_layers", ""), need(head, "scratch", "")
+        projects, resize, scratch = need(head, "projects"), need(head, "resize_layers"), need(head, "scratch")
         if len(projects) != 4 or len(resize) != 4:
             fail("projects", f"{len(projects)} projections / {len(resize)} resize layers: the head fuses four levels")
         self.proj, self.resize = [], []
@@ -301,8 +293,8 @@ class FusedDPTHead(_FusedHead):
             self.output_dim = oc2[2].out_channels
             if not 2 <= self.output_dim <= 8:
                 fail("scratch.output_conv2[2]", f"output_dim {self.output_dim}: gd_dpt_head_out serves 2 .. 8")
-            self.w_last = _f32(oc2[2].weight.reshape(self.output_dim, -1))
-            self.b_last = _f32(oc2[2].bias) if oc2[2].bias is not None else torch.zeros(self.output_dim, dtype=torch.float32, device=oc2[2].weight.device)
+            self.w_last = f32(oc2[2].weight.reshape(self.output_dim, -1))
+            self.b_last = f32(oc2[2].bias) if oc2[2].bias is not None else torch.zeros(self.output_dim, dtype=torch.float32, device=oc2[2].weight.device)
         self._tables = {}
 
     # ------------------------------------------------------------------------------------------------------------------------------
@@ -399,12 +391,12 @@ class FusedMASt3RHead(_FusedHead):
         super().__init__(dtype, name)
         fail, need, conv = self._fail, self._need, self._pack_conv
         # ---- the postprocess: MASt3R's, recognised by the attributes it reads
-        if not need(head, "postprocess", ""):
+        if not need(head, "postprocess"):
             fail("postprocess", "missing: the fused head returns the postprocessed dict (pts3d, conf, desc, desc_conf), not the raw map")
-        self.patch, self.D = int(need(head, "patch_size", "")), int(need(head, "local_feat_dim", ""))
-        self.two_confs = bool(need(head, "two_confs", ""))
-        depth_mode, conf_mode, desc_mode = need(head, "depth_mode", ""), need(head, "conf_mode", ""), need(head, "desc_mode", "")
-        desc_conf_mode = need(head, "desc_conf_mode", "")
+        self.patch, self.D = int(need(head, "patch_size")), int(need(head, "local_feat_dim"))
+        self.two_confs = bool(need(head, "two_confs"))
+        depth_mode, desc_mode = need(head, "depth_mode"), need(head, "desc_mode")
+        conf_mode, desc_conf_mode = need(head, "conf_mode"), need(head, "desc_conf_mode")      # None: no confidence / as conf_mode
         if not (isinstance(depth_mode, (tuple, list)) and len(depth_mode) == 3 and depth_mode[0] in ops.MH_PTS):
             fail("depth_mode", f"{depth_mode!r}: served are (mode, -inf, inf) with mode in {sorted(ops.MH_PTS)}")
         if depth_mode[1] != -float("inf") or depth_mode[2] != float("inf"):
@@ -429,7 +421,7 @@ class FusedMASt3RHead(_FusedHead):
         else:
             self.desc_conf_mode = self.conf_mode
         # ---- the DPT adapter
-        dpt = need(head, "dpt", "")
+        dpt = need(head, "dpt")
         if getattr(dpt, "head_type", "regression") != "regression":
             fail("dpt.head_type", f"{dpt.head_type!r}: served is 'regression'")
         self.hooks = [int(i) for i in need(dpt, "hooks", "dpt")]
@@ -476,13 +468,12 @@ class FusedMASt3RHead(_FusedHead):
         self.c_out1, self.od = seq[0].out_channels, seq[4].out_channels
         if self.od != 3 + (self.conf_mode is not None):
             fail("dpt.head[4]", f"{self.od} output channels with conf_mode {conf_mode!r}: served are 3 (pts3d) without, 4 (pts3d + confidence) with a conf_mode")
-        self.w_last = _f32(seq[4].weight.reshape(self.od, -1))
-        self.b_last = _f32(seq[4].bias) if seq[4].bias is not None else torch.zeros(self.od, dtype=torch.float32, device=seq[4].weight.device)
+        self.w_last = f32(seq[4].weight.reshape(self.od, -1))
+        self.b_last = f32(seq[4].bias) if seq[4].bias is not None else torch.zeros(self.od, dtype=torch.float32, device=seq[4].weight.device)
         # ---- the local-feature MLP: fc1 + GELU, fc2 with its rows in the kernel's (i, j, c) order
-        mlp = need(head, "head_local_features", "")
+        mlp = need(head, "head_local_features")
         fc1, fc2, act = need(mlp, "fc1", "head_local_features"), need(mlp, "fc2", "head_local_features"), need(mlp, "act", "head_local_features")
-        if not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
-            fail("head_local_features.act", f"is {type(act).__name__}: served is the erf-form GELU")
+        self._r.exact_gelu(act, "head_local_features.act")
         for m, attr in ((fc1, "head_local_features.fc1"), (fc2, "head_local_features.fc2")):
             if not isinstance(m, torch.nn.Linear):
                 fail(attr, f"is {type(m).__name__}, not a Linear")
@@ -494,9 +485,9 @@ class FusedMASt3RHead(_FusedHead):
         if not 1 <= self.patch <= 16:
             fail("patch_size", f"{self.patch}: gd_mast3r_head_out serves 1 .. 16")
         zeros = lambda m: torch.zeros(m.out_features, dtype=torch.float32, device=m.weight.device)
-        self.fc1 = (self._to_op(fc1.weight), _f32(fc1.bias) if fc1.bias is not None else zeros(fc1))
+        self.fc1 = (self._to_op(fc1.weight), f32(fc1.bias) if fc1.bias is not None else zeros(fc1))
         self.fc2 = (self._to_op(pack_pixel_shuffle(fc2.weight.detach(), self.patch)),
-                    pack_pixel_shuffle(_f32(fc2.bias) if fc2.bias is not None else zeros(fc2), self.patch))
+                    pack_pixel_shuffle(f32(fc2.bias) if fc2.bias is not None else zeros(fc2), self.patch))
 
     def _rows(self, t, B, n, what):
         if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 3 and t.shape[0] == B and t.shape[1] == n):
@@ -549,10 +540,6 @@ class FusedMASt3RHead(_FusedHead):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # The camera head
 # ----------------------------------------------------------------------------------------------------------------------------------
-def _exact_gelu(m):
-    return isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none"
-
-
 class FusedCameraHead:
     """FusedCameraHead(camera_head)(tokens_list) -> the module's list of [B, S, 9] encodings (vggt/heads/camera_head.py:83-154 CameraHead), on the
     few-row kernels of csrc/rows.hip and gd_layernorm_fwd; `poses(tokens_list, image_hw)` also returns the decoded cameras
@@ -575,33 +562,9 @@ class FusedCameraHead:
         if dtype not in (torch.float32, torch.bfloat16):
             raise GdHipError(f"FusedCameraHead: dtype {dtype}: torch.float32 or torch.bfloat16")
         self.name, self.dtype, m = name, dtype, camera_head
-
-        def fail(attr, why):
-            raise GdHipError(f"FusedCameraHead: {name}.{attr}: {why}")
-
-        def need(obj, attr, where=""):
-            if getattr(obj, attr, None) is None:
-                fail(where + attr, "missing")
-            return getattr(obj, attr)
-        f32 = lambda t: t.detach().float().contiguous()
+        r = Reader("FusedCameraHead", name)
+        fail, need, ln, linear, no_dropout = r.fail, r.need, r.ln, r.linear, r.no_dropout
         wt = lambda t: t.detach().to(dtype).contiguous()
-
-        def ln(mod, attr, width):
-            if not (isinstance(mod, torch.nn.LayerNorm) and mod.elementwise_affine and mod.weight is not None and mod.bias is not None) or \
-                    tuple(mod.normalized_shape) != (width,):
-                fail(attr, f"not an affine LayerNorm({width}) with a bias")
-            return (f32(mod.weight), f32(mod.bias), float(mod.eps))
-
-        def linear(mod, attr, k, n=None, cast=f32):
-            if not isinstance(mod, torch.nn.Linear) or mod.in_features != k or (n is not None and mod.out_features != n):
-                fail(attr, f"not a Linear({k} -> {'.' if n is None else n})")
-            b = f32(mod.bias) if mod.bias is not None else None
-            return (cast(mod.weight), b)
-
-        def no_dropout(mod, attr):
-            p = float(getattr(mod, "p", 0.0)) if mod is not None else 0.0
-            if p != 0.0 and getattr(mod, "training", False):
-                fail(attr, f"p = {p} in training mode: the kernels have no dropout")
 
         def scale(mod, attr, width):
             if isinstance(mod, torch.nn.Identity):
@@ -628,7 +591,7 @@ class FusedCameraHead:
         # embed_pose's K = 9 padded to 12 with zero columns; the raw encoding is kept as [M, 12] rows with columns 9..11 at 0
         w12 = torch.zeros(D, 12, dtype=torch.float32, device=embed.weight.device)
         w12[:, :9] = embed.weight.detach().float()
-        self.embed = (w12, f32(embed.bias) if embed.bias is not None else None)
+        self.embed = (w12, f32(embed.bias))
         ept = need(m, "empty_pose_tokens")
         if ept.numel() != 9:
             fail("empty_pose_tokens", f"{tuple(ept.shape)}: not 9 values")
@@ -646,44 +609,42 @@ class FusedCameraHead:
         self.trunk_norm = ln(need(m, "trunk_norm"), "trunk_norm", D)
         self.blocks = []
         for i, blk in enumerate(need(m, "trunk")):
-            w = f"trunk[{i}]."
+            w, wa, wm = f"trunk[{i}]", f"trunk[{i}].attn", f"trunk[{i}].mlp"
             at = need(blk, "attn", w)
             if getattr(at, "rope", None) is not None:
-                fail(w + "attn.rope", "set: gd_rows_attention has no rotary embedding")
+                fail(f"{wa}.rope", "set: gd_rows_attention has no rotary embedding")
             for nm in ("q_norm", "k_norm"):
                 if not isinstance(getattr(at, nm, None), torch.nn.Identity):
-                    fail(w + "attn." + nm, f"{type(getattr(at, nm, None)).__name__}: not Identity (qk_norm is not served)")
-            H = int(need(at, "num_heads", w + "attn."))
+                    fail(f"{wa}.{nm}", f"{type(getattr(at, nm, None)).__name__}: not Identity (qk_norm is not served)")
+            H = int(need(at, "num_heads", wa))
             hd = D // H if H >= 1 and D % H == 0 else 0
             if hd % 4 or not 4 <= hd <= 256:
-                fail(w + "attn.num_heads", f"{H}: head dimension {D / H if H else None}; gd_rows_attention serves multiples of 4 from 4 to 256")
-            no_dropout(getattr(at, "attn_drop", None), w + "attn.attn_drop")
-            no_dropout(getattr(at, "proj_drop", None), w + "attn.proj_drop")
+                fail(f"{wa}.num_heads", f"{H}: head dimension {D / H if H else None}; gd_rows_attention serves multiples of 4 from 4 to 256")
+            no_dropout(getattr(at, "attn_drop", None), f"{wa}.attn_drop")
+            no_dropout(getattr(at, "proj_drop", None), f"{wa}.proj_drop")
             mlp = need(blk, "mlp", w)
-            if not _exact_gelu(getattr(mlp, "act", None)):
-                fail(w + "mlp.act", f"{getattr(mlp, 'act', None)}: the epilogue serves exact (erf) GELU")
-            no_dropout(getattr(mlp, "drop", None), w + "mlp.drop")
-            fc1 = linear(need(mlp, "fc1", w + "mlp."), w + "mlp.fc1", D, None, wt)
+            r.exact_gelu(getattr(mlp, "act", None), f"{wm}.act")
+            no_dropout(getattr(mlp, "drop", None), f"{wm}.drop")
+            fc1 = linear(need(mlp, "fc1", wm), f"{wm}.fc1", D, None, wt)
             hidden = fc1[0].shape[0]
             if hidden % 8:
-                fail(w + "mlp.fc1", f"hidden width {hidden}: a multiple of 8 is served")
-            self.blocks.append(dict(H=H, scale=float(getattr(at, "scale", hd ** -0.5)), norm1=ln(need(blk, "norm1", w), w + "norm1", D),
-                                    norm2=ln(need(blk, "norm2", w), w + "norm2", D), qkv=linear(need(at, "qkv", w + "attn."), w + "attn.qkv", D, 3 * D, wt),
-                                    proj=linear(need(at, "proj", w + "attn."), w + "attn.proj", D, D, wt), fc1=fc1,
-                                    fc2=linear(need(mlp, "fc2", w + "mlp."), w + "mlp.fc2", hidden, D, wt),
-                                    ls1=scale(need(blk, "ls1", w), w + "ls1", D), ls2=scale(need(blk, "ls2", w), w + "ls2", D)))
+                fail(f"{wm}.fc1", f"hidden width {hidden}: a multiple of 8 is served")
+            self.blocks.append(dict(H=H, scale=float(getattr(at, "scale", hd ** -0.5)), norm1=ln(need(blk, "norm1", w), f"{w}.norm1", D),
+                                    norm2=ln(need(blk, "norm2", w), f"{w}.norm2", D), qkv=linear(need(at, "qkv", wa), f"{wa}.qkv", D, 3 * D, wt),
+                                    proj=linear(need(at, "proj", wa), f"{wa}.proj", D, D, wt), fc1=fc1,
+                                    fc2=linear(need(mlp, "fc2", wm), f"{wm}.fc2", hidden, D, wt),
+                                    ls1=scale(need(blk, "ls1", w), f"{w}.ls1", D), ls2=scale(need(blk, "ls2", w), f"{w}.ls2", D)))
         if not self.blocks:
             fail("trunk", "empty")
         self.hidden = max(b["fc1"][0].shape[0] for b in self.blocks)
         pb = need(m, "pose_branch")
-        if not _exact_gelu(getattr(pb, "act", None)):
-            fail("pose_branch.act", f"{getattr(pb, 'act', None)}: the epilogue serves exact (erf) GELU")
+        r.exact_gelu(getattr(pb, "act", None), "pose_branch.act")
         no_dropout(getattr(pb, "drop", None), "pose_branch.drop")
-        self.pb1 = linear(need(pb, "fc1", "pose_branch."), "pose_branch.fc1", D)
+        self.pb1 = linear(need(pb, "fc1", "pose_branch"), "pose_branch.fc1", D)
         self.pbh = self.pb1[0].shape[0]
         if self.pbh % 4:
             fail("pose_branch.fc1", f"hidden width {self.pbh}: a multiple of 4 is served")
-        self.pb2 = linear(need(pb, "fc2", "pose_branch."), "pose_branch.fc2", self.pbh, 9)
+        self.pb2 = linear(need(pb, "fc2", "pose_branch"), "pose_branch.fc2", self.pbh, 9)
         self.weight_bytes = sum(t.numel() * t.element_size() for t in self._weights())        # streamed once per iteration
         self._ws, self.launches = {}, 0
 
@@ -695,10 +656,8 @@ class FusedCameraHead:
     def _to(self, device):
         if self.empty.device == device:
             return
-        mv = lambda v: v.to(device) if torch.is_tensor(v) else tuple(mv(u) for u in v) if isinstance(v, tuple) else v
-        for n in ("embed", "empty", "modulation", "token_norm", "trunk_norm", "pb1", "pb2"):
-            setattr(self, n, mv(getattr(self, n)))
-        self.blocks = [{k: mv(v) for k, v in b.items()} for b in self.blocks]
+        for n in ("embed", "empty", "modulation", "token_norm", "trunk_norm", "pb1", "pb2", "blocks"):
+            setattr(self, n, to_device(getattr(self, n), device))
         self._ws = {}
 
     def _workspace(self, M, device):

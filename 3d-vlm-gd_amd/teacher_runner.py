@@ -98,6 +98,21 @@ def _no_attention_maps(attn_modules):
             del m.forward            # drop the instance attribute: the class's forward is visible again
 
 
+@contextlib.contextmanager
+def _shadowed(*triples):
+    """For the duration of the block, each (object, name, value) is an instance attribute that shadows the class's method of that name (a
+    module's `forward`, the matcher's `_decoder`): the user's own code drives the fused path.  Deleted again, last first, however the block ends."""
+    done = []
+    try:
+        for obj, name, value in triples:
+            setattr(obj, name, value)
+            done.append((obj, name))
+        yield
+    finally:
+        for obj, name in reversed(done):
+            delattr(obj, name)                      # the class's own attribute is visible again
+
+
 class VGGTTeacherRunner:
     """vggt: a model shaped like vggt.models.vggt.VGGT (aggregator with `global_blocks`, `attn_indices`, `aa_block_size`,
     `temperature`; camera_head, depth_head, point_head, track_head).  `pose_decoder(pose_enc, image_hw) -> (extrinsic, intrinsic)`
@@ -192,16 +207,11 @@ class VGGTTeacherRunner:
                     tokens, pos = self._block_inputs(rgb_vggt)
             tokens_list, maps = self.fused.forward(tokens, pos, B, S)
             return tokens_list, agg.patch_start_idx, maps
-        # with fused_patch_embed, for this call only, an instance attribute shadows the embedder's forward: the user's aggregator drives the fused embedder
-        if self.embed is not None:
-            agg.patch_embed.forward = self.embed.forward
-        try:
-            with QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
-                with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
-                    tokens_list, ps_idx, _ = agg(rgb_vggt)
-        finally:
-            if self.embed is not None:
-                del agg.patch_embed.forward          # the class's own forward is visible again
+        # with fused_patch_embed, for this call only, the user's aggregator drives the fused embedder
+        shadow = [(agg.patch_embed, "forward", self.embed.forward)] if self.embed is not None else []
+        with _shadowed(*shadow), QKCapture(self.sel) as cap, _no_attention_maps(self.sel):
+            with torch.autocast("cuda", dtype=self.dtype, enabled=rgb_vggt.is_cuda):
+                tokens_list, ps_idx, _ = agg(rgb_vggt)
         qk = [(q.to(self.dtype) if q.dtype not in (torch.float32, torch.bfloat16) else q,
                k.to(self.dtype) if k.dtype not in (torch.float32, torch.bfloat16) else k) for q, k in cap.pairs()]
         return tokens_list, ps_idx, qk
@@ -239,15 +249,10 @@ class VGGTTeacherRunner:
                 else:
                     trk, _, _ = self.tracker(kp1[None], m.track_head.feature_extractor(tokens_list, rgb_vggt, ps_idx), iters=iters)
                 return trk[-1][0][1]
-            # with fused heads, for this call only, an instance attribute shadows the feature extractor's forward: the user's track_head drives the fused head
-            fe = m.track_head.feature_extractor if heads else None
-            if fe is not None:
-                fe.forward = heads["track_head.feature_extractor"].forward
-            try:
+            # with fused heads, for this call only, the user's track_head drives the fused feature extractor
+            shadow = [(m.track_head.feature_extractor, "forward", heads["track_head.feature_extractor"].forward)] if heads else []
+            with _shadowed(*shadow):
                 trk, _, _ = m.track_head(tokens_list, rgb_vggt, ps_idx, query_points=kp1[None])
-            finally:
-                if fe is not None:
-                    del fe.forward          # the class's own forward is visible again
             return trk[-1][0][1]
         fused = self.fused is not None
         scale = float(self.sel[0].scale) if hasattr(self.sel[0], "scale") else (64 if fused else qk[0][0].shape[-1]) ** -0.5
@@ -298,31 +303,22 @@ class MASt3RTeacherRunner:
         # lets TeacherTargetCache(keep_logits=True) follow the annealed temperature without another teacher forward
         fused = self.fused
         seen, dec = [], fused.decode if fused is not None else getattr(self.matcher, "_decoder", None)
-        shadowed = []                                   # (object, name) of the instance attributes set here
-
-        def shadow(obj, name, value):
-            setattr(obj, name, value)
-            shadowed.append((obj, name))
-        try:
-            if self.keep_logits and dec is not None:
-                def wrapped(*a, **k):
-                    r = dec(*a, **k)
-                    if isinstance(r, tuple) and len(r) == 3:
-                        seen.append((r[1], r[2]))
-                    return r
-                shadow(self.matcher, "_decoder", wrapped)
-            elif fused is not None:
-                shadow(self.matcher, "_decoder", dec)
-            if fused is not None:
-                for i, blk in enumerate(self.matcher.enc_blocks):
-                    shadow(blk, "forward", fused.encode if i == 0 else (lambda x, pos=None: x))
-            for n, head in (self.heads or {}).items():
-                shadow(getattr(self.matcher, n), "forward", head.forward)
+        shadow = []                                     # (object, name, value): see _shadowed
+        if self.keep_logits and dec is not None:
+            def wrapped(*a, **k):
+                r = dec(*a, **k)
+                if isinstance(r, tuple) and len(r) == 3:
+                    seen.append((r[1], r[2]))
+                return r
+            shadow.append((self.matcher, "_decoder", wrapped))
+        elif fused is not None:
+            shadow.append((self.matcher, "_decoder", dec))
+        if fused is not None:
+            shadow += [(blk, "forward", fused.encode if i == 0 else (lambda x, pos=None: x)) for i, blk in enumerate(self.matcher.enc_blocks)]
+        shadow += [(getattr(self.matcher, n), "forward", head.forward) for n, head in (self.heads or {}).items()]
+        with _shadowed(*shadow):
             out = inf(mk([rgb_mast3r_1, rgb_mast3r_2], scene_graph="complete", prefilter=None, symmetrize=True), self.matcher, device,
                       verbose=False)
-        finally:
-            for obj, name in reversed(shadowed):
-                delattr(obj, name)                      # the instance attribute shadowing the method: the class's own is visible again
         p1, p2 = out["pred1"], out["pred2"]
         dev = torch.device(device)
         recip = tg.mast3r_recip_logits([t.to(dev) for t in seen[-1][0]], [t.to(dev) for t in seen[-1][1]]) if seen else None

@@ -21,18 +21,15 @@ fp32 only.  The loop feeds its coordinates back through sin(~970 * flow) (utils.
 about an order of magnitude per iteration; with the reference's own modules, fp32 against fp64 already differs by up to a pixel after four iterations at
 unit-scale `flow_head` weights.  A 16-bit operand mode would start that growth from 2^-9 instead of 2^-24 and is not offered.
 
-The module stays the user's: this class reads its parameters (duck-typed on the attribute names, as teacher_blocks._BlockParams does) and refuses, naming the
+The module stays the user's: this class reads its parameters (duck-typed on the attribute names, through teacher_read.Reader as teacher_blocks._ViTBlock does) and refuses, naming the
 attribute, anything the kernels do not serve.  Off by default (teacher_runner.VGGTTeacherRunner(fused_tracker=True))."""
 import torch
 
 from . import ops
 from ._lib import GdHipError
+from .teacher_read import Reader, f32, to_device
 
 C_LATENT, MAX_RADIUS, MAX_LEVELS = 128, 4, 8
-
-
-def _exact_gelu(m):
-    return isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none"
 
 
 def level_sizes(H, W, levels):
@@ -52,15 +49,13 @@ def check_levels(H, W, levels, who="FusedTracker"):
                              f"({levels} levels need sides of at least {2 ** levels})")
 
 
-def _ln_params(m, attr, fail, width=None):
-    if not (isinstance(m, torch.nn.LayerNorm) and m.elementwise_affine and m.weight is not None and m.bias is not None) or \
-            (width is not None and tuple(m.normalized_shape) != (width,)):
-        fail(attr, f"not an affine LayerNorm{'' if width is None else f'({width})'} with a bias")
-    return (m.weight.detach().float().contiguous(), m.bias.detach().float().contiguous(), float(m.eps))
-
-
 def _lin_bias(b, n, like):
-    return b.detach().float().contiguous() if b is not None else torch.zeros(n, dtype=torch.float32, device=like.device)
+    """The tracker's linear layers always hand their kernel a bias vector: zeros where the module has none."""
+    return f32(b) if b is not None else torch.zeros(n, dtype=torch.float32, device=like.device)
+
+
+def _bias(lin):
+    return _lin_bias(lin.bias, lin.out_features, lin.weight)
 
 
 LINEAR_KINDS = ("gemm_nt", "tokens")
@@ -105,15 +100,8 @@ class FusedUpdateFormer:
     def __init__(self, former, name="updateformer", *, linear="gemm_nt"):
         self.name = name
         self.linear = _linear_kind(linear, f"FusedUpdateFormer: {name}")
-
-        def fail(attr, why):
-            raise GdHipError(f"FusedUpdateFormer: {name}.{attr}: {why}")
-
-        def need(obj, attr, where=""):
-            if getattr(obj, attr, None) is None:
-                fail(where + attr, "missing")
-            return getattr(obj, attr)
-        f32 = lambda t: t.detach().float().contiguous()
+        r = Reader("FusedUpdateFormer", name)
+        fail, need = r.fail, r.need
         it, fh = need(former, "input_transform"), need(former, "flow_head")
         if not isinstance(it, torch.nn.Linear) or not isinstance(fh, torch.nn.Linear) or fh.in_features != it.out_features:
             fail("input_transform / flow_head", "not Linear(input -> hidden) and Linear(hidden -> output)")
@@ -122,9 +110,9 @@ class FusedUpdateFormer:
         for attr, K in (("input_transform", self.Din), ("flow_head", D)):
             if K % 4:
                 fail(attr, f"K = {K}: the fp32 GEMM takes K in multiples of 4")
-        self.input_norm = _ln_params(need(former, "input_norm"), "input_norm", fail, self.Din)
-        self.output_norm = _ln_params(need(former, "output_norm"), "output_norm", fail, D)
-        self.input_transform = (f32(it.weight), _lin_bias(it.bias, D, it.weight))
+        self.input_norm = r.ln(need(former, "input_norm"), "input_norm", self.Din)
+        self.output_norm = r.ln(need(former, "output_norm"), "output_norm", D)
+        self.input_transform = (f32(it.weight), _bias(it))
         # flow_head's rows are padded to a multiple of 4 with zeros: the [M, ld] result is handed on as its first Dout columns, without a copy
         self.ldo = (self.Dout + 3) // 4 * 4
         wf = torch.zeros(self.ldo, D, dtype=torch.float32, device=fh.weight.device)
@@ -154,17 +142,16 @@ class FusedUpdateFormer:
             self.virtual, self.every, sv, p2v, v2p = None, 1, [], [], []
         if not time_blocks:
             fail("time_blocks", "empty")
-        self.time_blocks = [self._block(b, f"time_blocks[{i}]", False, fail, need) for i, b in enumerate(time_blocks)]
-        self.space_virtual_blocks = [self._block(b, f"space_virtual_blocks[{i}]", False, fail, need) for i, b in enumerate(sv)]
-        self.space_point2virtual_blocks = [self._block(b, f"space_point2virtual_blocks[{i}]", True, fail, need) for i, b in enumerate(p2v)]
-        self.space_virtual2point_blocks = [self._block(b, f"space_virtual2point_blocks[{i}]", True, fail, need) for i, b in enumerate(v2p)]
+        self.time_blocks = [self._block(r, b, f"time_blocks[{i}]", False) for i, b in enumerate(time_blocks)]
+        self.space_virtual_blocks = [self._block(r, b, f"space_virtual_blocks[{i}]", False) for i, b in enumerate(sv)]
+        self.space_point2virtual_blocks = [self._block(r, b, f"space_point2virtual_blocks[{i}]", True) for i, b in enumerate(p2v)]
+        self.space_virtual2point_blocks = [self._block(r, b, f"space_virtual2point_blocks[{i}]", True) for i, b in enumerate(v2p)]
         self.launches = 0
 
-    def _block(self, blk, where, cross, fail, need):
-        D = self.D
-        f32 = lambda t: t.detach().float().contiguous()
+    def _block(self, r, blk, where, cross):
+        D, fail, need = self.D, r.fail, r.need
         aname = where + (".cross_attn" if cross else ".attn")
-        at = need(blk, "cross_attn" if cross else "attn", where + ".")
+        at = need(blk, "cross_attn" if cross else "attn", where)
         if not isinstance(at, torch.nn.MultiheadAttention):
             fail(aname, f"{type(at).__name__}: not a torch.nn.MultiheadAttention")
         if not at.batch_first:
@@ -185,20 +172,18 @@ class FusedUpdateFormer:
         hd = D // H
         if hd % 4 or not 4 <= hd <= 64:
             fail(aname + ".num_heads", f"{H}: head dimension {hd}; gd_attention_small_fwd serves multiples of 4 from 4 to 64")
-        mlp = need(blk, "mlp", where + ".")
-        fc1, fc2 = need(mlp, "fc1", where + ".mlp."), need(mlp, "fc2", where + ".mlp.")
-        if not _exact_gelu(getattr(mlp, "act", None)):
-            fail(where + ".mlp.act", f"{getattr(mlp, 'act', None)}: the GEMM epilogue serves exact (erf) GELU")
+        mlp = need(blk, "mlp", where)
+        fc1, fc2 = need(mlp, "fc1", where + ".mlp"), need(mlp, "fc2", where + ".mlp")
+        r.exact_gelu(getattr(mlp, "act", None), where + ".mlp.act")
         if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear)) or fc1.in_features != D or fc2.in_features != fc1.out_features or \
                 fc2.out_features != D or fc1.out_features % 4:
             fail(where + ".mlp", f"fc1 / fc2 do not map {D} -> hidden (a multiple of 4) -> {D}")
         w, b = f32(at.in_proj_weight), _lin_bias(at.in_proj_bias, 3 * D, at.in_proj_weight)
-        p = dict(H=H, cross=cross, norm1=_ln_params(need(blk, "norm1", where + "."), where + ".norm1", fail, D),
-                 norm2=_ln_params(need(blk, "norm2", where + "."), where + ".norm2", fail, D),
-                 out=(f32(at.out_proj.weight), _lin_bias(at.out_proj.bias, D, at.in_proj_weight)),
-                 fc1=(f32(fc1.weight), _lin_bias(fc1.bias, fc1.out_features, fc1.weight)), fc2=(f32(fc2.weight), _lin_bias(fc2.bias, D, fc2.weight)))
+        norm = lambda nm: r.ln(need(blk, nm, where), f"{where}.{nm}", D)
+        p = dict(H=H, cross=cross, norm1=norm("norm1"), norm2=norm("norm2"), out=(f32(at.out_proj.weight), _bias(at.out_proj)),
+                 fc1=(f32(fc1.weight), _bias(fc1)), fc2=(f32(fc2.weight), _bias(fc2)))
         if cross:
-            p["norm_context"] = _ln_params(need(blk, "norm_context", where + "."), where + ".norm_context", fail, D)
+            p["norm_context"] = norm("norm_context")
             p["q"], p["kv"] = (w[:D].contiguous(), b[:D].contiguous()), (w[D:].contiguous(), b[D:].contiguous())
         else:
             p["qkv"] = (w, b)
@@ -208,15 +193,9 @@ class FusedUpdateFormer:
     def _to(self, device):
         if self.flow_head[0].device == device:
             return
-        mv = lambda v: v.to(device) if torch.is_tensor(v) else tuple(mv(u) for u in v) if isinstance(v, tuple) else v
-        for n in ("input_norm", "output_norm", "input_transform", "flow_head"):
-            setattr(self, n, mv(getattr(self, n)))
-        if self.virtual is not None:
-            self.virtual = self.virtual.to(device)
-        for blocks in (self.time_blocks, self.space_virtual_blocks, self.space_point2virtual_blocks, self.space_virtual2point_blocks):
-            for p in blocks:
-                for k in p:
-                    p[k] = mv(p[k])
+        for n in ("input_norm", "output_norm", "input_transform", "flow_head", "virtual", "time_blocks", "space_virtual_blocks",
+                  "space_point2virtual_blocks", "space_virtual2point_blocks"):
+            setattr(self, n, to_device(getattr(self, n), device))
 
     def _ln(self, x, p):
         self.launches += 1
@@ -334,15 +313,8 @@ class FusedTracker:
     def __init__(self, tracker, name="tracker", fused_updateformer=False, *, linear="gemm_nt"):
         self.name = name
         self.linear = _linear_kind(linear, f"FusedTracker: {name}")
-
-        def fail(attr, why):
-            raise GdHipError(f"FusedTracker: {name}.{attr}: {why}")
-
-        def need(obj, attr, where=""):
-            if getattr(obj, attr, None) is None:
-                fail(where + attr, "missing")
-            return getattr(obj, attr)
-        f32 = lambda t: t.detach().float().contiguous()
+        r = Reader("FusedTracker", name)
+        fail, need = r.fail, r.need
         C = int(need(tracker, "latent_dim"))
         if C != C_LATENT:
             fail("latent_dim", f"{C}: the tracker kernels serve {C_LATENT}")
@@ -355,19 +327,15 @@ class FusedTracker:
         self.stride, self.max_scale = need(tracker, "stride"), float(need(tracker, "max_scale"))
         if self.max_scale == 0:
             fail("max_scale", "0")
-        fn = need(tracker, "fmap_norm")
-        if not (isinstance(fn, torch.nn.LayerNorm) and fn.elementwise_affine and fn.bias is not None and tuple(fn.normalized_shape) == (C,)):
-            fail("fmap_norm", f"not an affine LayerNorm({C})")
-        self.fmap_norm = (f32(fn.weight), f32(fn.bias), float(fn.eps))
+        self.fmap_norm = r.ln(need(tracker, "fmap_norm"), "fmap_norm", C)
         gn = need(tracker, "ffeat_norm")
         if not (isinstance(gn, torch.nn.GroupNorm) and gn.affine and gn.num_groups == 1 and gn.num_channels == C):
             fail("ffeat_norm", f"not an affine GroupNorm(1, {C})")
         self.ffeat_norm = (f32(gn.weight), f32(gn.bias), float(gn.eps))
         # corr_mlp: Linear(levels * (2r+1)^2 -> hidden), exact GELU, Linear(hidden -> C); K is padded to the fp32 GEMM's 128-byte K steps
         mlp = need(tracker, "corr_mlp")
-        fc1, fc2 = need(mlp, "fc1", "corr_mlp."), need(mlp, "fc2", "corr_mlp.")
-        if not _exact_gelu(getattr(mlp, "act", None)):
-            fail("corr_mlp.act", f"{getattr(mlp, 'act', None)}: the GEMM epilogue serves exact (erf) GELU")
+        fc1, fc2 = need(mlp, "fc1", "corr_mlp"), need(mlp, "fc2", "corr_mlp")
+        r.exact_gelu(getattr(mlp, "act", None), "corr_mlp.act")
         K = self.levels * (2 * self.radius + 1) ** 2
         if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear)) or fc1.in_features != K or fc2.in_features != fc1.out_features or \
                 fc2.out_features != C:
@@ -377,15 +345,14 @@ class FusedTracker:
         self._gemm_ok("corr_mlp.fc2", fc2.in_features, fail)
         w1 = torch.zeros(fc1.out_features, self.kpad, dtype=torch.float32, device=fc1.weight.device)
         w1[:, :K] = fc1.weight.detach().float()
-        self.corr_mlp = (w1, self._bias(fc1), f32(fc2.weight), self._bias(fc2))
+        self.corr_mlp = (w1, _bias(fc1), f32(fc2.weight), _bias(fc2))
         up = need(tracker, "ffeat_updater")
         mods = list(up) if isinstance(up, torch.nn.Sequential) else []
         if len(mods) != 2 or not isinstance(mods[0], torch.nn.Linear) or mods[0].in_features != C or mods[0].out_features != C:
             fail("ffeat_updater", f"not Sequential(Linear({C}, {C}), GELU)")
-        if not _exact_gelu(mods[1]):
-            fail("ffeat_updater[1]", f"{mods[1]}: the GEMM epilogue serves exact (erf) GELU")
+        r.exact_gelu(mods[1], "ffeat_updater[1]")
         self._gemm_ok("ffeat_updater[0]", C, fail)
-        self.ffeat_updater = (f32(mods[0].weight), self._bias(mods[0]))
+        self.ffeat_updater = (f32(mods[0].weight), _bias(mods[0]))
         self.updateformer = need(tracker, "updateformer")
         if fused_updateformer:
             self.updateformer = FusedUpdateFormer(self.updateformer, name=f"{name}.updateformer", linear=linear)
@@ -421,11 +388,7 @@ class FusedTracker:
         if self.qrt.device != device:
             self.qrt = self.qrt.to(device)
             for n in self._TENSORS:
-                setattr(self, n, tuple(v.to(device) if torch.is_tensor(v) else v for v in getattr(self, n)))
-
-    @staticmethod
-    def _bias(lin):
-        return lin.bias.detach().float().contiguous() if lin.bias is not None else torch.zeros(lin.out_features, dtype=torch.float32, device=lin.weight.device)
+                setattr(self, n, to_device(getattr(self, n), device))
 
     @staticmethod
     def _gemm_ok(attr, K, fail):

@@ -5,6 +5,7 @@ import ctypes
 
 import pytest
 import torch
+import torch.nn as nn
 
 import croco_layout as CL
 from test_teacher_runner_ref import fill_params
@@ -88,3 +89,89 @@ def test_cross_attention_argument_guards():
     assert _call(L, 1, 16, 1 << 20, 16, 64, 1024, 2048, _lib.BF16) != 0 and "2^31" in err() and "kv rows" in err()
     assert _call(L, 1, 16, 16, 2, 64, 130, 256, _lib.BF16) != 0 and "16 bytes" in err()               # 260-byte rows
     assert _call(L, 1, 16, 16, 2, 64, 128, 256, 7) != 0 and "dtype" in err()
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# FusedCroCoBlocks: what it refuses, at construction, naming the block and the attribute (no device)
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _edit(path, value):
+    def edit(m):
+        obj, names = m, path.split(".")
+        for n in names[:-1]:
+            obj = obj[int(n)] if n.isdigit() else getattr(obj, n)
+        setattr(obj, names[-1], value)
+    return edit
+
+
+def _drop(path):
+    def edit(m):
+        obj, names = m, path.split(".")
+        for n in names[:-1]:
+            obj = obj[int(n)] if n.isdigit() else getattr(obj, n)
+        delattr(obj, names[-1])
+    return edit
+
+
+CROCO_REFUSALS = [
+    ({}, _drop("enc_blocks.0.attn"), r"enc_blocks\[0\].*attn"),
+    ({}, _drop("dec_blocks.1.mlp"), r"dec_blocks\[1\].*mlp"),
+    ({}, _drop("enc_blocks.1.norm1"), r"enc_blocks\[1\].*norm1"),
+    ({}, _drop("dec_blocks2.0.cross_attn"), r"dec_blocks2\[0\].*cross_attn"),
+    ({}, _drop("dec_blocks.0.norm_y"), r"dec_blocks\[0\].*norm_y"),
+    ({}, _drop("dec_blocks.0.cross_attn.projq"), r"dec_blocks\[0\].*cross_attn.*projq"),
+    ({}, _drop("enc_blocks.0.mlp.fc1"), r"enc_blocks\[0\].*fc1"),
+    (dict(enc_heads=6), None, r"enc_blocks\[0\].*head dim 32"),
+    ({}, _edit("dec_blocks.0.attn.scale", 0.2), r"dec_blocks\[0\].*attn\.scale"),
+    ({}, _edit("dec_blocks.1.cross_attn.scale", 0.2), r"dec_blocks\[1\].*cross_attn\.scale"),
+    ({}, _edit("enc_blocks.1.attn.rope", None), r"enc_blocks\[1\].*attn\.rope"),
+    ({}, _edit("dec_blocks2.1.cross_attn.rope", None), r"dec_blocks2\[1\].*cross_attn\.rope"),
+    ({}, _edit("enc_blocks.0.mlp.act", nn.GELU(approximate="tanh")), r"enc_blocks\[0\].*mlp\.act"),
+    ({}, _edit("dec_blocks2.1.mlp.act", nn.ReLU()), r"dec_blocks2\[1\].*mlp\.act"),
+    ({}, _edit("dec_blocks.0.norm3", nn.LayerNorm(128, elementwise_affine=False)), r"dec_blocks\[0\].*norm3"),
+    ({}, _edit("dec_blocks.1.norm2", nn.LayerNorm(64)), r"dec_blocks\[1\].*norm2"),
+    ({}, _edit("enc_blocks.1.norm2", nn.Identity()), r"enc_blocks\[1\].*norm2"),
+    ({}, _edit("dec_blocks2.0.norm_y", nn.BatchNorm1d(128)), r"dec_blocks2\[0\].*norm_y"),
+    ({}, _edit("dec_blocks.0.cross_attn.num_heads", 1), r"dec_blocks\[0\].*cross_attn.*head dim 128"),
+    ({}, _edit("dec_blocks.1.cross_attn.rope", CL.DeviceRope2D(10.0)), r"dec_blocks\[1\].*cross_attn.*RoPE base"),
+    ({}, _edit("dec_blocks.0.cross_attn.projv", nn.Linear(128, 128, bias=False)), r"dec_blocks\[0\].*cross_attn\.projk"),
+    (dict(dec_depth2=1), None, r"dec_blocks.*dec_blocks2"),
+    (dict(dec_depth=0), None, r"dec_blocks"),
+    ({}, _edit("decoder_embed", nn.Identity()), r"decoder_embed"),
+    ({}, _edit("decoder_embed", nn.Linear(192, 64)), r"dec_blocks\[0\].*width 128"),
+    ({}, _drop("dec_norm"), r"dec_norm"),
+    ({}, _edit("dec_norm", nn.LayerNorm(128, elementwise_affine=False)), r"dec_norm"),
+    ({}, _drop("enc_blocks"), r"enc_blocks"),
+]
+
+
+@pytest.mark.parametrize("case", range(len(CROCO_REFUSALS)))
+def test_fused_croco_blocks_refuse_what_the_kernels_do_not_serve(case):
+    import gd_amd  # noqa: F401
+    from gd_amd._lib import GdHipError
+    from gd_amd.teacher_blocks import FusedCroCoBlocks
+    over, edit, match = CROCO_REFUSALS[case]
+    m = CL.CrocoLayout(**dict(CL.CFG, **over)).eval()
+    if edit is not None:
+        FusedCroCoBlocks(m)                                                              # accepted as it stands
+        edit(m)
+    with pytest.raises(GdHipError, match=match) as e:
+        FusedCroCoBlocks(m)
+    print(e.value)
+    assert str(e.value).startswith("FusedCroCoBlocks: ")
+    with pytest.raises(GdHipError, match="dtype"):
+        FusedCroCoBlocks(CL.CrocoLayout(**CL.CFG), dtype=torch.float16)
+
+
+def test_fused_croco_blocks_accept_identity_norm_y_and_biasless_cross_projections():
+    import gd_amd  # noqa: F401
+    from gd_amd.teacher_blocks import FusedCroCoBlocks
+    m = CL.CrocoLayout(**CL.CFG).eval()
+    m.dec_blocks[1].norm_y = nn.Identity()                                               # norm_mem=False
+    ca = m.dec_blocks2[0].cross_attn
+    ca.projk, ca.projv = nn.Linear(128, 128, bias=False), nn.Linear(128, 128, bias=False)
+    f = FusedCroCoBlocks(m, dtype=torch.bfloat16)
+    assert f.dec1[1].ny is None and f.dec1[0].ny is not None and f.dec2[0].bkv is None
+    p = f.dec1[0]
+    assert p.wkv.shape == (256, 128) and p.wkv.dtype == torch.bfloat16 and p.bkv.shape == (256,) and p.bkv.dtype == torch.float32
+    assert torch.equal(p.wkv[128:], m.dec_blocks[0].cross_attn.projv.weight.detach().to(torch.bfloat16))
+    assert (p.H, p.C, p.base) == (2, 128, 100.0) and (f.enc[0].H, f.enc[0].C) == (3, 192)

@@ -77,6 +77,20 @@ def test_refusals_name_the_attribute(what, dtype, no_hip):
     assert f"depth_head.{attr}:" in str(e.value) and word in str(e.value)
 
 
+@pytest.mark.parametrize("attr", ["pos_embed", "feature_only", "down_ratio"])
+def test_a_present_none_attribute_is_the_modules_own_value_not_a_missing_one(attr, no_hip):
+    """Only an absent attribute is missing: None stands for False in the two flags, and down_ratio is not read before the first call."""
+    m = DL.make_head("a")
+    setattr(m, attr, None)
+    h = teacher_heads.FusedDPTHead(m, name="depth_head")
+    assert getattr(h, attr) in (False, None)
+    m = DL.make_head("a")
+    m.__dict__.pop(attr, None)
+    if not hasattr(m, attr):
+        with pytest.raises(GdHipError, match=rf"depth_head\.{attr}: missing"):
+            teacher_heads.FusedDPTHead(m, name="depth_head")
+
+
 def test_served_heads_construct_without_a_hip_call(no_hip):
     for case in DL.CASES:
         for dtype in (torch.float32, torch.bfloat16):
